@@ -12,9 +12,15 @@ CUs that step k's MFCC tail and FFN leave idle; every step still runs its
 whole clip through both kernels inside the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--ffn bl13|ref39] [--streams S]
+                    [--dump-outputs DIR] [--full]
 
 Rank 0 prints ONE JSON line.  `value` = frames (MFCC frames) processed by all
-ranks / max-over-ranks wall time of the K timed steps.  `roofline` is for the
+ranks / max-over-ranks wall time of the K timed steps, and `ms_per_step` that
+wall time per step.  A plain run sets up, warms up, times the K steps and
+prints that line; --dump-outputs DIR also writes the labels of the last timed
+step to DIR/labels.npy (float32; the inputs are seeded, so two builds can be
+compared label for label).  Everything else is measured with --full only, in
+runs of its own after the timed steps.  `roofline` is for the
 dominant kernel (the MFCC kernel): its average launch duration comes from HIP
 events on the stream it is launched on, around K back-to-back launches right
 after the timed region (events between the step's kernels would idle the GPU
@@ -66,6 +72,22 @@ def synth_audio(n_samples, seed, device):
     amp[torch.rand(n_seg, generator=g, device=device) < 0.05] = 0.0
     x = torch.randn(n_seg * seg, generator=g, device=device) * amp.repeat_interleave(seg)
     return x[:n_samples].round_().clamp_(-32767, 32767).contiguous()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy in float32, at most
+    DUMP_MAX_BYTES in all; a larger array is cut to a fixed, seeded sample of
+    its flattened elements (in index order)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // 4 // len(arrays)
+    for name, a in arrays.items():
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
 
 
 def cpu_baseline(layers, frames_per_chunk=20000, min_seconds=10.0, max_chunks=100):
@@ -388,8 +410,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)  # past the clock ramp of a cold GPU
     ap.add_argument("--frames", type=int, default=1_000_000)
     ap.add_argument("--ffn", default="bl13", choices=["bl13", "ref39"])
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")  # skip the C2 / C5 lines (profiling runs)
+    # a plain run times the K steps and prints the headline line; --full adds
+    # the serial and per-kernel timings, roofline, int16, gather, latency,
+    # C2 / C5 and CPU-baseline measurements (each takes runs of its own)
+    ap.add_argument("--full", action="store_true")
+    # write the last timed step's labels to DIR/labels.npy (float32)
+    ap.add_argument("--dump-outputs", metavar="DIR")
+    ap.add_argument("--no-cpu", action="store_true")  # with --full: skip the CPU baselines
+    ap.add_argument("--no-secondary", action="store_true")  # with --full: skip the C2 / C5 lines (profiling runs)
     # gloo: rehearse the N > 1 path on fewer GPUs than ranks (ranks share
     # devices round-robin; the labels travel through host memory)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
@@ -514,115 +542,106 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device=flag_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
-    # the same K steps strictly serial on one stream (no gathers): the latency
-    # of one clip through both kernels, beside the pipelined headline
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    ts = time.perf_counter()
-    for k in range(args.steps):
-        pipe.labels(audio, out=labels)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    ts = time.perf_counter() - ts
-    if world > 1:
-        t = torch.tensor([ts], dtype=torch.float64, device=flag_dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        ts = float(t.item())
-    # per-kernel launch durations, right after the timed region: HIP events
-    # around `steps` back-to-back launches of one kernel (an event record
-    # between two kernels idles the GPU for ~5 us, so the timed steps carry
-    # none)
-    # (batches of 10 launches between event pairs: the mean over all of them,
-    # and p10 / p50 / p90 of the batch means; at least 30 batches, so that one
-    # slow batch -- a clock dip, a neighbour's burst on the node -- moves the
-    # mean by a thirtieth of its excess rather than a tenth)
-    def kernel_ms(fn, batch=10):
-        nb = max(30, args.steps // batch)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(nb + 1)]
-        ev[0].record(stream)
-        for i in range(nb):
-            for _ in range(batch):
-                fn()
-            ev[i + 1].record(stream)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned to its caller: this rank's labels
+        # (N = 1), or every rank's as gathered on rank 0 (N > 1)
+        i = (k_step[0] - 1) % len(labs)
+        last = torch.stack([o.cpu() for o in gathers[i].out]) if world > 1 else labs[i].cpu()
+        dump_outputs(args.dump_outputs, {"labels": last.numpy()})
+    # everything below the headline figure takes runs of its own: --full only
+    if args.full:
+        # the same K steps strictly serial on one stream (no gathers): the latency
+        # of one clip through both kernels, beside the pipelined headline
+        if world > 1:
+            dist.barrier()
         torch.cuda.synchronize()
-        per = sorted(ev[i].elapsed_time(ev[i + 1]) / batch for i in range(nb))
-        pct = {f"p{q}": per[min(nb - 1, int(q / 100 * nb))] for q in (10, 50, 90)}
-        return ev[0].elapsed_time(ev[nb]) / (nb * batch), pct
-    # N > 1: the gather alone ("plus gather time"), every rank
-    # issuing `steps` back-to-back gathers of its F - 5 uint8 labels to rank 0,
-    # synchronised and max-reduced like the timed region; the timed steps
-    # above overlap each gather with the next step's kernels
-    gather = None
-    if world > 1:
-        n_g = max(10, args.steps)
-        dist.barrier()
+        ts = time.perf_counter()
+        for k in range(args.steps):
+            pipe.labels(audio, out=labels)
         torch.cuda.synchronize()
-        tg = time.perf_counter()
-        for _ in range(n_g):
-            gathers[0].start(labs[0], async_op=False)
+        if world > 1:
+            dist.barrier()
+        ts = time.perf_counter() - ts
+        if world > 1:
+            t = torch.tensor([ts], dtype=torch.float64, device=flag_dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            ts = float(t.item())
+        # per-kernel launch durations, right after the timed region: HIP events
+        # around `steps` back-to-back launches of one kernel (an event record
+        # between two kernels idles the GPU for ~5 us, so the timed steps carry
+        # none)
+        # (batches of 10 launches between event pairs: the mean over all of them,
+        # and p10 / p50 / p90 of the batch means; at least 30 batches, so that one
+        # slow batch -- a clock dip, a neighbour's burst on the node -- moves the
+        # mean by a thirtieth of its excess rather than a tenth)
+        def kernel_ms(fn, batch=10):
+            nb = max(30, args.steps // batch)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(nb + 1)]
+            ev[0].record(stream)
+            for i in range(nb):
+                for _ in range(batch):
+                    fn()
+                ev[i + 1].record(stream)
+            torch.cuda.synchronize()
+            per = sorted(ev[i].elapsed_time(ev[i + 1]) / batch for i in range(nb))
+            pct = {f"p{q}": per[min(nb - 1, int(q / 100 * nb))] for q in (10, 50, 90)}
+            return ev[0].elapsed_time(ev[nb]) / (nb * batch), pct
+        # N > 1: the gather alone ("plus gather time"), every rank
+        # issuing `steps` back-to-back gathers of its F - 5 uint8 labels to rank 0,
+        # synchronised and max-reduced like the timed region; the timed steps
+        # above overlap each gather with the next step's kernels
+        gather = None
+        if world > 1:
+            n_g = max(10, args.steps)
+            dist.barrier()
+            torch.cuda.synchronize()
+            tg = time.perf_counter()
+            for _ in range(n_g):
+                gathers[0].start(labs[0], async_op=False)
+            torch.cuda.synchronize()
+            dist.barrier()
+            tg = time.perf_counter() - tg
+            t = torch.tensor([tg], dtype=torch.float64, device=flag_dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            gather = {"gather_ms": float(t.item()) * 1e3 / n_g, "label_bytes_per_rank": F - 5,
+                      "collective": "gather" if gathers[0].use_gather else "all_gather",
+                      "backend": args.backend, "gathers_timed": n_g,
+                      "note": "standalone (host-timed, max over ranks); in the timed steps each gather "
+                              + ("overlaps the next step's kernels on RCCL's stream" if args.backend == "nccl"
+                                 else "runs through gloo's host path (rehearsal backend)")}
+        mfcc_ms, mfcc_pct = kernel_ms(lambda: pipe.mfcc(audio, out=mfcc))
+        ffn_ms, ffn_pct = kernel_ms(lambda: ffn_plan.window_labels(mfcc, out=labels))
+        # the fused single-kernel clip form (MFCC rows kept on chip) and the FFN
+        # on exact-f32 MFMA, beside the headline's forms
+        fused_ms, fused_pct = kernel_ms(lambda: pipe.labels(audio, out=labels, fused=True))
+        exact = FFNClassifier(layers, arith="f32")
+        ffn_f32_ms, _ = kernel_ms(lambda: exact.plan.window_labels(mfcc, out=labels))
+        del exact
+        # the same clip as int16 PCM (what vad.py reads; exact: the samples are
+        # integers in the int16 range), MFCC kernel only -- reported beside `value`
+        audio16 = audio.to(torch.int16)
+        mfcc16 = torch.empty_like(mfcc)
+        for _ in range(10):
+            pipe.mfcc(audio16, out=mfcc16)
+        mfcc16_ms, _ = kernel_ms(lambda: pipe.mfcc(audio16, out=mfcc16))
+        # the whole C3 step on that int16 clip (bit-identical labels, tested),
+        # pipelined over the same streams and label buffers as the headline;
+        # reported beside `value`, which stays the fp32-input step
+        def step16(k):
+            with torch.cuda.stream(streams[k % len(streams)]):
+                pipe.labels(audio16, out=labs[k % len(labs)])
+        for k in range(20):
+            step16(k)
         torch.cuda.synchronize()
-        dist.barrier()
-        tg = time.perf_counter() - tg
-        t = torch.tensor([tg], dtype=torch.float64, device=flag_dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        gather = {"gather_ms": float(t.item()) * 1e3 / n_g, "label_bytes_per_rank": F - 5,
-                  "collective": "gather" if gathers[0].use_gather else "all_gather",
-                  "backend": args.backend, "gathers_timed": n_g,
-                  "note": "standalone (host-timed, max over ranks); in the timed steps each gather "
-                          + ("overlaps the next step's kernels on RCCL's stream" if args.backend == "nccl"
-                             else "runs through gloo's host path (rehearsal backend)")}
-    mfcc_ms, mfcc_pct = kernel_ms(lambda: pipe.mfcc(audio, out=mfcc))
-    ffn_ms, ffn_pct = kernel_ms(lambda: ffn_plan.window_labels(mfcc, out=labels))
-    # the fused single-kernel clip form (MFCC rows kept on chip) and the FFN
-    # on exact-f32 MFMA, beside the headline's forms
-    fused_ms, fused_pct = kernel_ms(lambda: pipe.labels(audio, out=labels, fused=True))
-    exact = FFNClassifier(layers, arith="f32")
-    ffn_f32_ms, _ = kernel_ms(lambda: exact.plan.window_labels(mfcc, out=labels))
-    del exact
-    # the same clip as int16 PCM (what vad.py reads; exact: the samples are
-    # integers in the int16 range), MFCC kernel only -- reported beside `value`
-    audio16 = audio.to(torch.int16)
-    mfcc16 = torch.empty_like(mfcc)
-    for _ in range(10):
-        pipe.mfcc(audio16, out=mfcc16)
-    mfcc16_ms, _ = kernel_ms(lambda: pipe.mfcc(audio16, out=mfcc16))
-    # the whole C3 step on that int16 clip (bit-identical labels, tested),
-    # pipelined over the same streams and label buffers as the headline;
-    # reported beside `value`, which stays the fp32-input step
-    def step16(k):
-        with torch.cuda.stream(streams[k % len(streams)]):
-            pipe.labels(audio16, out=labs[k % len(labs)])
-    for k in range(20):
-        step16(k)
-    torch.cuda.synchronize()
-    t16 = time.perf_counter()
-    for k in range(args.steps):
-        step16(k)
-    torch.cuda.synchronize()
-    step16_ms = (time.perf_counter() - t16) * 1e3 / args.steps
-    del audio16
+        t16 = time.perf_counter()
+        for k in range(args.steps):
+            step16(k)
+        torch.cuda.synchronize()
+        step16_ms = (time.perf_counter() - t16) * 1e3 / args.steps
+        del audio16
 
     if rank == 0:
         value = world * F * args.steps / el
-        dom_ms, dom_bytes, dom = (mfcc_ms, MFCC_BYTES_PER_FRAME, "mfcc_kernel") \
-            if mfcc_ms >= ffn_ms else (ffn_ms, FFN_BYTES_PER_FRAME, "ffn_kernel")
-        achieved = dom_bytes * F / (dom_ms * 1e-3) / 1e9
-        # roofline.traffic is NOT measured in this run (a PMC pass cannot run
-        # inside the timed process): it is read from the committed rocprofv3
-        # --pmc FETCH_SIZE / WRITE_SIZE pass (profiles/pmc_traffic.json), and
-        # traffic_source says which run produced it
-        traffic, traffic_source = None, None
-        tp = os.path.join(REPO, "profiles", "pmc_traffic.json")
-        if os.path.exists(tp):
-            with open(tp) as f:
-                tj = json.load(f)
-            traffic = tj.get(dom, {}).get("hbm_bytes_per_launch")
-            if traffic is not None:
-                traffic_source = {"file": "profiles/pmc_traffic.json", "measured_in_this_run": False,
-                                  "run": tj.get("source"), "kernel": tj.get(dom, {}).get("kernel"),
-                                  "correction": tj.get("correction")}
         out = {
             "metric": "MFCC+FFN frames/sec on 16 kHz 25 ms/10 ms hop",
             "value": value,
@@ -634,9 +653,8 @@ def main():
             "ms_per_step": el * 1e3 / args.steps,
             "ms_per_step_note": (f"pipelined throughput: consecutive steps alternate over {args.streams} HIP "
                                  "streams, so a step's MFCC overlaps the previous step's FFN; "
-                                 "ms_per_step_serial is the same K steps on one stream")
+                                 "ms_per_step_serial (--full) is the same K steps on one stream")
             if args.streams > 1 else "steps serial on one stream",
-            "ms_per_step_serial": ts * 1e3 / args.steps,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -654,57 +672,78 @@ def main():
                        "frames_per_gpu": F, "ffn": "-".join(map(str, topo)),
                        "hip_streams": args.streams,
                        "parallelism": f"clip-shard x{world}"},
-            "roofline": {"bound": "hbm", "kernel": dom,
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": traffic_source,
-                         "frac_vs_measured_copy": achieved / HBM_COPY_GBS,
-                         "algorithmic_bytes_per_launch": dom_bytes * F,
-                         "avg_launch_ms": dom_ms},
-            # the MFCC kernel sits at the fp32 ridge (~20 flop/B): its VALU
-            # ceiling beside the HBM one
-            "compute": {"bound": "valu", "kernel": "mfcc_kernel",
-                        "achieved": MFCC_FLOPS_PER_FRAME * F / (mfcc_ms * 1e-3) / 1e12,
-                        "peak": VALU_PEAK_TFS, "unit": "TFLOP/s",
-                        "frac": MFCC_FLOPS_PER_FRAME * F / (mfcc_ms * 1e-3) / 1e12 / VALU_PEAK_TFS,
-                        "flops_per_frame": MFCC_FLOPS_PER_FRAME},
-            # the VALU time those instructions take at the measured rates,
-            # against the kernel's measured launch time
-            "valu_model": {"kernel": "mfcc_kernel",
-                           "packed_per_frame": MFCC_VALU_PACKED_PER_FRAME,
-                           "scalar_per_frame": MFCC_VALU_SCALAR_PER_FRAME,
-                           "ns_packed": VALU_NS_PACKED_2W, "ns_scalar": VALU_NS_SCALAR_2W,
-                           "model_ms": F / N_SIMDS * (MFCC_VALU_PACKED_PER_FRAME * VALU_NS_PACKED_2W
-                                                      + MFCC_VALU_SCALAR_PER_FRAME * VALU_NS_SCALAR_2W) * 1e-6,
-                           "frac_of_launch": F / N_SIMDS * (MFCC_VALU_PACKED_PER_FRAME * VALU_NS_PACKED_2W
-                                                            + MFCC_VALU_SCALAR_PER_FRAME * VALU_NS_SCALAR_2W)
-                           * 1e-6 / mfcc_ms},
-            "kernels_ms": {"mfcc_kernel": mfcc_ms, "ffn_kernel": ffn_ms,
-                           "ffn_kernel_exact_f32": ffn_f32_ms, "mfcc_ffn_fused_kernel": fused_ms},
-            "kernels_ms_pct": {"mfcc_kernel": mfcc_pct, "ffn_kernel": ffn_pct,
-                               "mfcc_ffn_fused_kernel": fused_pct},
-            "mfcc_int16_input": {"avg_launch_ms": mfcc16_ms,
-                                 "frames_per_s": F / (mfcc16_ms * 1e-3),
-                                 "c3_step_ms": step16_ms,
-                                 "c3_step_frames_per_s": world * F / (step16_ms * 1e-3) if world == 1 else None,
-                                 "note": "int16 PCM (vad.py's wav samples before astype(float32)): the same "
-                                         "clip, exact conversion, bit-identical MFCCs and labels",
-                                 "algorithmic_bytes_per_frame": 160 * 2 + 13 * 4,
-                                 "achieved_GBps": (160 * 2 + 13 * 4) * F / (mfcc16_ms * 1e-3) / 1e9},
         }
-        if gather is not None:
-            out["gather"] = gather
-        if world == 1:
-            out["feed_frame_latency"] = feed_frame_latency(dev)
-            if not args.no_secondary:
-                out["secondary_configs"] = secondary_configs(dev)
-        if world == 1 and not args.no_cpu:
-            out["cpu_baseline"] = cpu_baseline(layers)
-            out["cpu_baseline_all_cores"] = cpu_baseline_all(tuple(topo))
-            pf1, pfall = cpu_baseline_per_frame(tuple(topo))
-            out["cpu_baseline_per_frame"] = pf1
-            out["cpu_baseline_per_frame_all_cores"] = pfall
-            out["cpu_host"] = host_facts()
+        if args.full:
+            dom_ms, dom_bytes, dom = (mfcc_ms, MFCC_BYTES_PER_FRAME, "mfcc_kernel") \
+                if mfcc_ms >= ffn_ms else (ffn_ms, FFN_BYTES_PER_FRAME, "ffn_kernel")
+            achieved = dom_bytes * F / (dom_ms * 1e-3) / 1e9
+            # roofline.traffic is NOT measured in this run (a PMC pass cannot run
+            # inside the timed process): it is read from the committed rocprofv3
+            # --pmc FETCH_SIZE / WRITE_SIZE pass (profiles/pmc_traffic.json), and
+            # traffic_source says which run produced it
+            traffic, traffic_source = None, None
+            tp = os.path.join(REPO, "profiles", "pmc_traffic.json")
+            if os.path.exists(tp):
+                with open(tp) as f:
+                    tj = json.load(f)
+                traffic = tj.get(dom, {}).get("hbm_bytes_per_launch")
+                if traffic is not None:
+                    traffic_source = {"file": "profiles/pmc_traffic.json", "measured_in_this_run": False,
+                                      "run": tj.get("source"), "kernel": tj.get(dom, {}).get("kernel"),
+                                      "correction": tj.get("correction")}
+            out.update({
+                "ms_per_step_serial": ts * 1e3 / args.steps,
+                "roofline": {"bound": "hbm", "kernel": dom,
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                             "traffic_source": traffic_source,
+                             "frac_vs_measured_copy": achieved / HBM_COPY_GBS,
+                             "algorithmic_bytes_per_launch": dom_bytes * F,
+                             "avg_launch_ms": dom_ms},
+                # the MFCC kernel sits at the fp32 ridge (~20 flop/B): its VALU
+                # ceiling beside the HBM one
+                "compute": {"bound": "valu", "kernel": "mfcc_kernel",
+                            "achieved": MFCC_FLOPS_PER_FRAME * F / (mfcc_ms * 1e-3) / 1e12,
+                            "peak": VALU_PEAK_TFS, "unit": "TFLOP/s",
+                            "frac": MFCC_FLOPS_PER_FRAME * F / (mfcc_ms * 1e-3) / 1e12 / VALU_PEAK_TFS,
+                            "flops_per_frame": MFCC_FLOPS_PER_FRAME},
+                # the VALU time those instructions take at the measured rates,
+                # against the kernel's measured launch time
+                "valu_model": {"kernel": "mfcc_kernel",
+                               "packed_per_frame": MFCC_VALU_PACKED_PER_FRAME,
+                               "scalar_per_frame": MFCC_VALU_SCALAR_PER_FRAME,
+                               "ns_packed": VALU_NS_PACKED_2W, "ns_scalar": VALU_NS_SCALAR_2W,
+                               "model_ms": F / N_SIMDS * (MFCC_VALU_PACKED_PER_FRAME * VALU_NS_PACKED_2W
+                                                          + MFCC_VALU_SCALAR_PER_FRAME * VALU_NS_SCALAR_2W) * 1e-6,
+                               "frac_of_launch": F / N_SIMDS * (MFCC_VALU_PACKED_PER_FRAME * VALU_NS_PACKED_2W
+                                                                + MFCC_VALU_SCALAR_PER_FRAME * VALU_NS_SCALAR_2W)
+                               * 1e-6 / mfcc_ms},
+                "kernels_ms": {"mfcc_kernel": mfcc_ms, "ffn_kernel": ffn_ms,
+                               "ffn_kernel_exact_f32": ffn_f32_ms, "mfcc_ffn_fused_kernel": fused_ms},
+                "kernels_ms_pct": {"mfcc_kernel": mfcc_pct, "ffn_kernel": ffn_pct,
+                                   "mfcc_ffn_fused_kernel": fused_pct},
+                "mfcc_int16_input": {"avg_launch_ms": mfcc16_ms,
+                                     "frames_per_s": F / (mfcc16_ms * 1e-3),
+                                     "c3_step_ms": step16_ms,
+                                     "c3_step_frames_per_s": world * F / (step16_ms * 1e-3) if world == 1 else None,
+                                     "note": "int16 PCM (vad.py's wav samples before astype(float32)): the same "
+                                             "clip, exact conversion, bit-identical MFCCs and labels",
+                                     "algorithmic_bytes_per_frame": 160 * 2 + 13 * 4,
+                                     "achieved_GBps": (160 * 2 + 13 * 4) * F / (mfcc16_ms * 1e-3) / 1e9},
+            })
+            if gather is not None:
+                out["gather"] = gather
+            if world == 1:
+                out["feed_frame_latency"] = feed_frame_latency(dev)
+                if not args.no_secondary:
+                    out["secondary_configs"] = secondary_configs(dev)
+            if world == 1 and not args.no_cpu:
+                out["cpu_baseline"] = cpu_baseline(layers)
+                out["cpu_baseline_all_cores"] = cpu_baseline_all(tuple(topo))
+                pf1, pfall = cpu_baseline_per_frame(tuple(topo))
+                out["cpu_baseline_per_frame"] = pf1
+                out["cpu_baseline_per_frame_all_cores"] = pfall
+                out["cpu_host"] = host_facts()
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

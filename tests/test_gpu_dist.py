@@ -184,7 +184,7 @@ def test_bench_gpus_launches_ranks():
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo",
                         "--frames", "20000", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-secondary",
                         "--min-warmup-s", "0.05"],
                        capture_output=True, text=True, timeout=240, env=env, cwd=REPO)

@@ -21,7 +21,7 @@ for r in 1 2 3; do
 done
 for r in 1 2 3; do
   for L in base $V; do
-    VAD_AMD_LIB=vad_amd/lib/libvad_amd_$L.so timeout -k 10 200 python3 bench.py --no-cpu --no-secondary > $OUT/bench_${L}_r$r.json 2>>$OUT/err.log || exit 4
+    VAD_AMD_LIB=vad_amd/lib/libvad_amd_$L.so timeout -k 10 200 python3 bench.py --full --no-cpu --no-secondary > $OUT/bench_${L}_r$r.json 2>>$OUT/err.log || exit 4
     python3 -c "import json;d=json.load(open('$OUT/bench_${L}_r$r.json'));k=d['kernels_ms'];print('$L r$r', '%.4f ms/step'%d['ms_per_step'], 'mfcc %.1f ffn %.1f fused %.1f us'%(k['mfcc_kernel']*1e3,k['ffn_kernel']*1e3,k['mfcc_ffn_fused_kernel']*1e3))" | tee -a $OUT/bench.txt
   done
 done

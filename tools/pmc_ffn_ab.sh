@@ -11,7 +11,7 @@ for v in "$@"; do
   while read -r CTRS; do
     i=$((i + 1))
     VAD_AMD_LIB=vad_amd/lib/libvad_amd_$v.so timeout -s KILL 120 rocprofv3 --pmc $CTRS -d $OUT/$v/p$i -o run \
-      --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu > $OUT/$v.p$i.log 2>&1 || { tail -20 $OUT/$v.p$i.log; exit 1; }
+      --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu > $OUT/$v.p$i.log 2>&1 || { tail -20 $OUT/$v.p$i.log; exit 1; }
   done < tools/pmc_ffn.txt
 done
 python3 tools/pmc_ffn_report.py $OUT "$@" > $OUT/report.json && cat $OUT/report.json

@@ -4,7 +4,7 @@
 # Writes gpurun_out/prof_<tag>/{trace,pmc1..4}/ ; each pass runs under its own timeout.
 set -u
 TAG=$1; shift
-ARGS=${@:---steps 5 --warmup 2 --no-cpu}
+ARGS=${@:---full --steps 5 --warmup 2 --no-cpu}
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT

@@ -8,8 +8,8 @@ cd $R
 OUT=$R/gpurun_out/val_$TAG
 mkdir -p $OUT
 timeout -k 10 150 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29517 bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 --no-cpu --no-secondary \
+  --master-port 29517 bench.py --full --gpus 2 --backend gloo --steps 20 --warmup 5 --no-cpu --no-secondary \
   > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err || { tail -20 $OUT/bench_2rank_gloo.err; exit 9; }
 cat $OUT/bench_2rank_gloo.json
-bash tools/profile.sh $TAG --steps 5 --warmup 2 --no-cpu --no-secondary || exit 10
+bash tools/profile.sh $TAG --full --steps 5 --warmup 2 --no-cpu --no-secondary || exit 10
 echo all done
