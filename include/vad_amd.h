@@ -317,6 +317,22 @@ int vad_stream_hops(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* f
                     int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len, int64_t n_streams,
                     int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels,
                     int64_t label_block_stride, void* stream);
+/* The same three entries for int16 PCM hop samples (the live signal as it
+ * is recorded, vad.py:37): the arguments, checks and refusals of the f32
+ * entry, all strides in int16 elements; a row needs only 2-byte alignment
+ * (base, hop_stride, hop_block_stride and hop_len may be odd).  Each sample
+ * is converted by an exact (float) where it is loaded, so labels and state
+ * (frames, ring, count -- fp32 / int32 as above) are identical to the f32
+ * entry fed the same values as floats. */
+int vad_stream_push_hop_i16(float* frames, int64_t frame_stride, int32_t frame_len, const int16_t* hop,
+                            int64_t hop_stride, int32_t hop_len, int64_t n_streams, void* stream);
+int vad_stream_hop_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
+                       int32_t frame_len, const int16_t* hop, int64_t hop_stride, int32_t hop_len,
+                       int64_t n_streams, float* ring, int32_t* count, uint8_t* labels, void* stream);
+int vad_stream_hops_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
+                        int32_t frame_len, const int16_t* hop, int64_t hop_stride, int32_t hop_len,
+                        int64_t n_streams, int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count,
+                        uint8_t* labels, int64_t label_block_stride, void* stream);
 int vad_stream_step(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, const float* frames,
                     int64_t frame_stride, int32_t frame_len, int64_t n_streams, float* ring,
                     int32_t* count, uint8_t* labels, float* mfcc_scratch, void* stream);

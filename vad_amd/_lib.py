@@ -72,6 +72,11 @@ SIGNATURES = {
                                c_vp]),
     "vad_stream_hops": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32, c_i64, c_vp,
                                 c_vp, c_vp, c_i64, c_vp]),
+    "vad_stream_push_hop_i16": (c_int, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_vp]),
+    "vad_stream_hop_i16": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp,
+                                   c_vp]),
+    "vad_stream_hops_i16": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32, c_i64, c_vp,
+                                    c_vp, c_vp, c_i64, c_vp]),
     "vad_stream_step": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp,
                                 c_vp]),
     "vad_graph_launch": (c_int, [c_vp, c_vp]),

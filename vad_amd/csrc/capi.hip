@@ -873,21 +873,36 @@ int64_t vad_stream_ring_floats(int64_t n_streams, int32_t mfcc_n) {
   return n_streams * 5 * (int64_t)mfcc_n;
 }
 
-int vad_stream_push_hop(float* frames, int64_t frame_stride, int32_t frame_len, const float* hop,
-                        int64_t hop_stride, int32_t hop_len, int64_t n_streams, void* stream) {
+// The streaming entries take the hop samples as fp32 or as int16 PCM
+// (hop_bytes 4 / 2, strides in elements either way): one body each, the same
+// checks in the same order before any HIP call.
+static int stream_push_entry(float* frames, int64_t frame_stride, int32_t frame_len, const void* hop,
+                             int hop_bytes, int64_t hop_stride, int32_t hop_len, int64_t n_streams,
+                             void* stream) {
   if (n_streams < 0 || frame_len <= 0 || frame_len > 1024 || hop_len <= 0 || hop_len > frame_len ||
       frame_stride < frame_len || hop_stride < hop_len)
     return VAD_EINVAL;
   if (n_streams == 0) return VAD_OK;
   if (!frames || !hop) return VAD_EINVAL;
-  return (int)launch_stream_push(frames, frame_stride, frame_len, hop, hop_stride, hop_len, n_streams,
+  return (int)launch_stream_push(frames, frame_stride, frame_len, hop, hop_bytes, hop_stride, hop_len, n_streams,
                                  (hipStream_t)stream);
 }
 
-int vad_stream_hops(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
-                    int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len, int64_t n_streams,
-                    int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels,
-                    int64_t label_block_stride, void* stream) {
+int vad_stream_push_hop(float* frames, int64_t frame_stride, int32_t frame_len, const float* hop,
+                        int64_t hop_stride, int32_t hop_len, int64_t n_streams, void* stream) {
+  return stream_push_entry(frames, frame_stride, frame_len, hop, 4, hop_stride, hop_len, n_streams, stream);
+}
+
+int vad_stream_push_hop_i16(float* frames, int64_t frame_stride, int32_t frame_len, const int16_t* hop,
+                            int64_t hop_stride, int32_t hop_len, int64_t n_streams, void* stream) {
+  return stream_push_entry(frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len, n_streams, stream);
+}
+
+static int stream_hops_entry(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames,
+                             int64_t frame_stride, int32_t frame_len, const void* hop, int hop_bytes,
+                             int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,
+                             int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels,
+                             int64_t label_block_stride, void* stream) {
   if (!plan || !ffn || n_streams < 0 || n_hops < 0 || frame_len <= 0 || frame_len > 1024 || hop_len <= 0 ||
       hop_len > frame_len || frame_stride < frame_len || hop_stride < hop_len)
     return VAD_EINVAL;
@@ -905,9 +920,25 @@ int vad_stream_hops(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* f
   if (plan->generic()) return VAD_EUNSUPPORTED;  // its FFT is the 256-point Stockham of fft_n = 512
   if (plan->spec == kSpecWindow) return VAD_EUNSUPPORTED;  // its table blob carries no analysis window
   return (int)launch_stream_hop(plan->dev, plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps,
-                                ffn->net, frames, frame_stride, frame_len, hop, hop_stride, hop_len,
+                                ffn->net, frames, frame_stride, frame_len, hop, hop_bytes, hop_stride, hop_len,
                                 n_streams, plan->host.mfcc_n, ring, count, labels, n_hops, hop_block_stride,
                                 label_block_stride, (hipStream_t)stream);
+}
+
+int vad_stream_hops(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
+                    int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len, int64_t n_streams,
+                    int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels,
+                    int64_t label_block_stride, void* stream) {
+  return stream_hops_entry(plan, ffn, frames, frame_stride, frame_len, hop, 4, hop_stride, hop_len, n_streams,
+                           n_hops, hop_block_stride, ring, count, labels, label_block_stride, stream);
+}
+
+int vad_stream_hops_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
+                        int32_t frame_len, const int16_t* hop, int64_t hop_stride, int32_t hop_len,
+                        int64_t n_streams, int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count,
+                        uint8_t* labels, int64_t label_block_stride, void* stream) {
+  return stream_hops_entry(plan, ffn, frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len, n_streams,
+                           n_hops, hop_block_stride, ring, count, labels, label_block_stride, stream);
 }
 
 int vad_stream_hop(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
@@ -915,6 +946,13 @@ int vad_stream_hop(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* fr
                    float* ring, int32_t* count, uint8_t* labels, void* stream) {
   return vad_stream_hops(plan, ffn, frames, frame_stride, frame_len, hop, hop_stride, hop_len, n_streams, 1, 0,
                          ring, count, labels, 0, stream);
+}
+
+int vad_stream_hop_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
+                       int32_t frame_len, const int16_t* hop, int64_t hop_stride, int32_t hop_len,
+                       int64_t n_streams, float* ring, int32_t* count, uint8_t* labels, void* stream) {
+  return vad_stream_hops_i16(plan, ffn, frames, frame_stride, frame_len, hop, hop_stride, hop_len, n_streams, 1, 0,
+                             ring, count, labels, 0, stream);
 }
 
 int vad_stream_step(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, const float* frames,

@@ -15,21 +15,25 @@
 
 namespace vad {
 
-template <int NR>  // registers per lane: frame_len <= 64 NR
+// TH: the hop samples' type, float or int16_t (PCM as recorded, vad.py:37;
+// the (float) of an int16 is exact, so either type leaves the same frames).
+// An int16 row is only 2-byte aligned (odd base, odd strides): one 2-byte
+// load per sample, lane-contiguous as the fp32 loads are.
+template <int NR, class TH>  // registers per lane: frame_len <= 64 NR
 __global__ __launch_bounds__(256) void stream_push_kernel(float* __restrict__ frames, int64_t fstride,
-                                                          int len, const float* __restrict__ hop,
+                                                          int len, const TH* __restrict__ hop,
                                                           int64_t hstride, int hlen, int64_t n_streams) {
   const int lane = threadIdx.x & 63;
   const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (s >= n_streams) return;
   float* row = frames + s * fstride;
-  const float* h = hop + s * hstride;
+  const TH* h = hop + s * hstride;
   const int keep = len - hlen;
   float v[NR];
 #pragma unroll
   for (int i = 0; i < NR; ++i) {
     const int t = lane + 64 * i;
-    v[i] = t < keep ? row[t + hlen] : (t < len ? h[t - keep] : 0.f);
+    v[i] = t < keep ? row[t + hlen] : (t < len ? (float)h[t - keep] : 0.f);
   }
 #pragma unroll
   for (int i = 0; i < NR; ++i) {
@@ -38,17 +42,26 @@ __global__ __launch_bounds__(256) void stream_push_kernel(float* __restrict__ fr
   }
 }
 
-hipError_t launch_stream_push(float* frames, int64_t fstride, int len, const float* hop, int64_t hstride,
-                              int hlen, int64_t n_streams, hipStream_t st) {
+template <class TH>
+static hipError_t launch_stream_push_t(float* frames, int64_t fstride, int len, const TH* hop, int64_t hstride,
+                                       int hlen, int64_t n_streams, hipStream_t st) {
   if (n_streams <= 0) return hipSuccess;
   const dim3 grid((unsigned)((n_streams + 3) / 4));
   if (len <= 64 * 7)
-    hipLaunchKernelGGL(stream_push_kernel<7>, grid, dim3(256), 0, st, frames, fstride, len, hop, hstride,
+    hipLaunchKernelGGL((stream_push_kernel<7, TH>), grid, dim3(256), 0, st, frames, fstride, len, hop, hstride,
                        hlen, n_streams);
   else
-    hipLaunchKernelGGL(stream_push_kernel<16>, grid, dim3(256), 0, st, frames, fstride, len, hop, hstride,
+    hipLaunchKernelGGL((stream_push_kernel<16, TH>), grid, dim3(256), 0, st, frames, fstride, len, hop, hstride,
                        hlen, n_streams);
   return hipGetLastError();
+}
+
+// hop: fp32 samples (hop_bytes 4) or int16 PCM (2); strides in elements
+hipError_t launch_stream_push(float* frames, int64_t fstride, int len, const void* hop, int hop_bytes,
+                              int64_t hstride, int hlen, int64_t n_streams, hipStream_t st) {
+  if (hop_bytes == 2)
+    return launch_stream_push_t(frames, fstride, len, (const int16_t*)hop, hstride, hlen, n_streams, st);
+  return launch_stream_push_t(frames, fstride, len, (const float*)hop, hstride, hlen, n_streams, st);
 }
 
 // Optional pre-emphasis (not in the reference pipeline, mfcc.py:59-61; the
@@ -177,12 +190,15 @@ __device__ __forceinline__ float2 w256(const float2* __restrict__ tw, int m) {
 
 // NR: 64-sample chunks of the frame a lane holds (7: frames up to 448
 // samples, the reference's 400; 16: up to 1024) -- the frame and the next
-// hop's samples stay in registers across hops, so the bound matters
-template <int NR>
+// hop's samples stay in registers across hops, so the bound matters.
+// TH: the hop samples' type (float, or int16_t PCM converted by an exact
+// (float) where it is loaded -- the two sites that read `hop`; frames, ring
+// and counts are fp32 either way, and everything after the load is one code)
+template <int NR, class TH>
 __global__ __launch_bounds__(1024) void stream_hop_kernel(const float* __restrict__ blob, int blob_n, int nf,
                                                           int n_taps, FfnDev net,
                                                           float* __restrict__ frames, int64_t fstride, int len,
-                                                          const float* __restrict__ hop, int64_t hstride,
+                                                          const TH* __restrict__ hop, int64_t hstride,
                                                           int hlen, int64_t n_streams, int mfcc_n,
                                                           float* __restrict__ ring, int* __restrict__ count,
                                                           uint8_t* __restrict__ labels, int n_hops,
@@ -234,7 +250,7 @@ __global__ __launch_bounds__(1024) void stream_hop_kernel(const float* __restric
   for (int i = 0; i < NR; ++i) {
     const int t = lane + 64 * i;
     v[i] = t < len ? row[t] : 0.f;
-    hn[i] = (t >= keep && t < len) ? hop[sc * hstride + (t - keep)] : 0.f;
+    hn[i] = (t >= keep && t < len) ? (float)hop[sc * hstride + (t - keep)] : 0.f;
   }
   int c = count[sc];
   float* rs = ring + sc * 5 * mfcc_n;
@@ -300,11 +316,11 @@ __global__ __launch_bounds__(1024) void stream_hop_kernel(const float* __restric
     }
     asm volatile("" ::: "memory");
     if (k + 1 < n_hops) {  // the next hop's samples, in flight during this one
-      const float* hs = hop + (int64_t)(k + 1) * hop_kstride + s * hstride;
+      const TH* hs = hop + (int64_t)(k + 1) * hop_kstride + s * hstride;
 #pragma unroll
       for (int i = 0; i < NR; ++i) {
         const int t = ln + 64 * i;
-        hn[i] = (t >= keep && t < len) ? hs[t - keep] : 0.f;
+        hn[i] = (t >= keep && t < len) ? (float)hs[t - keep] : 0.f;
       }
     }
     uint8_t* lab_k = labels + (int64_t)k * lab_kstride;
@@ -486,12 +502,12 @@ __global__ __launch_bounds__(1024) void stream_hop_kernel(const float* __restric
   if (lane == 0) count[s] = c;
 }
 
-hipError_t launch_stream_hop(const MfccDev* plan, const float* blob, int blob_n, int nf, int n_taps,
-                             const FfnDev& net, float* frames, int64_t fstride, int len, const float* hop,
-                             int64_t hstride, int hlen, int64_t n_streams, int mfcc_n, float* ring, int* count,
-                             uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
-                             hipStream_t st) {
-  (void)plan;
+template <class TH>
+static hipError_t launch_stream_hop_t(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net,
+                                      float* frames, int64_t fstride, int len, const TH* hop, int64_t hstride,
+                                      int hlen, int64_t n_streams, int mfcc_n, float* ring, int* count,
+                                      uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
+                                      hipStream_t st) {
   if (n_streams <= 0 || n_hops <= 0) return hipSuccess;
   const size_t tables = (size_t)(blob_n + net.wraw_n) * sizeof(float);
   // streams per block: at least VAD_HOP_MIN_WAVES (one wave per SIMD), then
@@ -520,23 +536,37 @@ hipError_t launch_stream_hop(const MfccDev* plan, const float* blob, int blob_n,
   while (waves > 1 && tables + (size_t)waves * kHopWaveFloats * sizeof(float) > 160 * 1024) waves >>= 1;
   const size_t smem = tables + (size_t)waves * kHopWaveFloats * sizeof(float);
   if (smem > 160 * 1024) return hipErrorInvalidValue;
-  static std::atomic<unsigned long long> attr_done{0};
+  static std::atomic<unsigned long long> attr_done{0};  // per hop type: these are the template's own
   static std::atomic<unsigned long long> attr_done16{0};
   const bool small = len <= 7 * 64;
-  const void* fn = small ? reinterpret_cast<const void*>(&stream_hop_kernel<7>)
-                         : reinterpret_cast<const void*>(&stream_hop_kernel<16>);
+  const void* fn = small ? reinterpret_cast<const void*>(&stream_hop_kernel<7, TH>)
+                         : reinterpret_cast<const void*>(&stream_hop_kernel<16, TH>);
   const hipError_t e = ensure_dyn_lds(fn, 160 * 1024, small ? attr_done : attr_done16);
   if (e != hipSuccess) return e;
   const dim3 grid((unsigned)((n_streams + waves - 1) / waves));
   if (small)
-    hipLaunchKernelGGL(stream_hop_kernel<7>, grid, dim3(64 * waves), smem, st, blob, blob_n, nf, n_taps, net, frames,
+    hipLaunchKernelGGL((stream_hop_kernel<7, TH>), grid, dim3(64 * waves), smem, st, blob, blob_n, nf, n_taps, net, frames,
                        fstride, len, hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride,
                        lab_kstride);
   else
-    hipLaunchKernelGGL(stream_hop_kernel<16>, grid, dim3(64 * waves), smem, st, blob, blob_n, nf, n_taps, net, frames,
+    hipLaunchKernelGGL((stream_hop_kernel<16, TH>), grid, dim3(64 * waves), smem, st, blob, blob_n, nf, n_taps, net, frames,
                        fstride, len, hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride,
                        lab_kstride);
   return hipGetLastError();
+}
+
+// hop: fp32 samples (hop_bytes 4) or int16 PCM (2); strides in elements
+hipError_t launch_stream_hop(const MfccDev* plan, const float* blob, int blob_n, int nf, int n_taps,
+                             const FfnDev& net, float* frames, int64_t fstride, int len, const void* hop,
+                             int hop_bytes, int64_t hstride, int hlen, int64_t n_streams, int mfcc_n, float* ring,
+                             int* count, uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
+                             hipStream_t st) {
+  (void)plan;
+  if (hop_bytes == 2)
+    return launch_stream_hop_t(blob, blob_n, nf, n_taps, net, frames, fstride, len, (const int16_t*)hop, hstride,
+                               hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, st);
+  return launch_stream_hop_t(blob, blob_n, nf, n_taps, net, frames, fstride, len, (const float*)hop, hstride, hlen,
+                             n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, st);
 }
 
 }  // namespace vad

@@ -31,6 +31,23 @@ static input block ``inputs`` (K, S, hop) and whose labels land in
 registers from hop to hop); capture() records one block into a hipGraph that
 reads ``inputs`` in place, so a producer that writes the next block there
 (e.g. an H2D copy of the audio devices' buffers) replays with no copy at all.
+
+int16 PCM: StreamBatch(..., input_dtype=torch.int16) takes the samples as
+they are recorded (vad.py:37, recoder.py:24-25 cast them afterwards):
+``inputs`` / ``hop_in`` / ``host_inputs`` are int16, step() / step_block()
+read int16 device tensors in place (vad_stream_hops_i16, one 2-byte load per
+sample, any element offset and stride), and the H2D copy of a block moves
+half the bytes.  The kernels convert with an exact (float) on load; frames,
+ring and counts stay fp32, so labels and state equal the fp32 batch's bit
+for bit.
+
+Blocks in flight: host_pipeline(depth) returns a HostPipeline with `depth`
+slots, each with pinned host buffers and a device input / label block of its
+own, and three streams (copy-in, compute, copy-out): submit(d) enqueues slot
+d's H2D, kernel(s) and D2H, event-ordered, so block k+1's copy-in and block
+k-1's copy-out overlap block k's kernel; wait(d) blocks the host on slot d's
+D2H only.  All kernels run on the one compute stream in submit order: the
+stream state carries exactly as in serial steps.
 """
 from __future__ import annotations
 
@@ -61,7 +78,9 @@ def hop_rows_disjoint(n_streams, n_hops, block_stride, hop_stride, hop_len):
 class StreamBatch:
 
     def __init__(self, n_streams, ffn, cfg: MfccConfig = MfccConfig(), device=None, kernel="hop",
-                 hops_per_step=1):
+                 hops_per_step=1, input_dtype=torch.float32):
+        if input_dtype not in (torch.float32, torch.int16):
+            raise ValueError("input_dtype must be torch.float32 or torch.int16")
         if not isinstance(ffn, FFNClassifier):
             ffn = FFNClassifier(ffn)
         if cfg.preemph is not None:
@@ -80,9 +99,12 @@ class StreamBatch:
         if K < 1:
             raise ValueError("hops_per_step must be >= 1")
         self.K = K
+        self.input_dtype = input_dtype
+        self._i16 = input_dtype == torch.int16
+        self._dtype_name = "int16" if self._i16 else "float32"
         self.frames = torch.zeros((S, L), dtype=torch.float32, device=dev)
         # static graph inputs / outputs: K hops of new samples, K label rows
-        self.inputs = torch.zeros((K, S, H), dtype=torch.float32, device=dev)
+        self.inputs = torch.zeros((K, S, H), dtype=input_dtype, device=dev)
         self.hop_in = self.inputs[0]
         self.ring = torch.zeros((S, 5, C), dtype=torch.float32, device=dev)
         self.count = torch.zeros((S,), dtype=torch.int32, device=dev)
@@ -95,7 +117,8 @@ class StreamBatch:
         self.host_labels = None
 
     def prime(self, carry):
-        """Set the last frame_size - hop samples of every stream (S, L-H)."""
+        """Set the last frame_size - hop samples of every stream (S, L-H),
+        float32 or int16 (converted exactly: the frames are fp32)."""
         L, H = self.cfg.frame_size, self.cfg.hop
         self.frames[:, H:].copy_(carry)
 
@@ -105,13 +128,16 @@ class StreamBatch:
         self.count.zero_()
         self.label_block.fill_(255)
 
-    def _hop_call(self, h, n_hops=1, labels=None):
-        """vad_stream_hops with the per-batch arguments prepared once (the
-        Python side of a launch is a few microseconds of ctypes marshalling:
-        per call only the hop block's address and strides change)."""
+    def _hop_call(self, h, n_hops=1, labels=None, stream=None):
+        """vad_stream_hops (_i16 for an int16 batch) with the per-batch
+        arguments prepared once (the Python side of a launch is a few
+        microseconds of ctypes marshalling: per call only the hop block's
+        address and strides change).  stream: a hipStream_t pointer, default
+        the current stream."""
         if getattr(self, "_hop_head", None) is None:
             L = self.cfg.frame_size
-            self._hop_fn = _lib.lib().vad_stream_hops
+            self._hop_fn = _lib.lib().vad_stream_hops_i16 if self._i16 else _lib.lib().vad_stream_hops
+            self._hop_name = "vad_stream_hops_i16" if self._i16 else "vad_stream_hops"
             self._hop_head = (self.plan.handle, self.ffn.plan.handle, _lib.ptr(self.frames), L, L)
             self._hop_mid = (_lib.ptr(self.ring), _lib.ptr(self.count))
             self._hop_labels = {}
@@ -123,19 +149,21 @@ class StreamBatch:
             self._hop_labels[key] = tail
         rc = self._hop_fn(*self._hop_head, ctypes.c_void_p(h.data_ptr()), h.stride(-2), self.cfg.hop, self.n,
                           n_hops, h.stride(0) if h.dim() == 3 else 0, *self._hop_mid, *tail,
-                          _lib.stream_ptr())
+                          _lib.stream_ptr() if stream is None else stream)
         if rc:
-            _lib.check(rc, "vad_stream_hops")
+            _lib.check(rc, self._hop_name)
 
-    def _three(self, h, labels):
+    def _three(self, h, labels, stream=None):
         L, H = self.cfg.frame_size, self.cfg.hop
         lib = _lib.lib()
-        _lib.check(lib.vad_stream_push_hop(_lib.ptr(self.frames), L, L, ctypes.c_void_p(h.data_ptr()), h.stride(0),
-                                           H, self.n, _lib.stream_ptr()), "vad_stream_push_hop")
+        st = _lib.stream_ptr() if stream is None else stream
+        push = lib.vad_stream_push_hop_i16 if self._i16 else lib.vad_stream_push_hop
+        _lib.check(push(_lib.ptr(self.frames), L, L, ctypes.c_void_p(h.data_ptr()), h.stride(0), H, self.n, st),
+                   "vad_stream_push_hop_i16" if self._i16 else "vad_stream_push_hop")
         _lib.check(lib.vad_stream_step(
             self.plan.handle, self.ffn.plan.handle, _lib.ptr(self.frames), L, L, self.n,
             _lib.ptr(self.ring), _lib.ptr(self.count), ctypes.c_void_p(labels.data_ptr()),
-            _lib.ptr(self.scratch), _lib.stream_ptr()), "vad_stream_step")
+            _lib.ptr(self.scratch), st), "vad_stream_step")
 
     def _body(self, hop=None):
         """One hop (K = 1) from `hop` or the static input."""
@@ -154,13 +182,15 @@ class StreamBatch:
                 self._three(self.inputs[k], self.label_block[k])
 
     def step(self, new_samples=None):
-        """Advance every stream by one hop (new_samples: (S, hop) device fp32;
-        None: the hop already written into ``hop_in``).  hops_per_step == 1."""
+        """Advance every stream by one hop (new_samples: (S, hop) device
+        tensor of the batch's input dtype; None: the hop already written into
+        ``hop_in``).  hops_per_step == 1."""
         if self.K != 1:
             raise ValueError("this batch advances hops_per_step hops at a time: use step_block")
         if new_samples is not None and (new_samples.shape != self.hop_in.shape
-                                        or new_samples.dtype != torch.float32 or not new_samples.is_cuda):
-            raise ValueError(f"new_samples must be a CUDA float32 tensor of shape {tuple(self.hop_in.shape)}")
+                                        or new_samples.dtype != self.input_dtype or not new_samples.is_cuda):
+            raise ValueError(f"new_samples must be a CUDA {self._dtype_name} tensor of shape "
+                             f"{tuple(self.hop_in.shape)}")
         if self.graph is not None and not self.graph_host_io:
             if new_samples is not None:
                 self.hop_in.copy_(new_samples)
@@ -175,12 +205,13 @@ class StreamBatch:
 
     def step_block(self, new_samples=None):
         """Advance every stream by K = hops_per_step hops; new_samples: (K, S,
-        hop) device fp32, or None when the block was written into ``inputs``
+        hop) device tensor of the batch's input dtype, or None when the block was written into ``inputs``
         (the graph's static input: no copy).  Returns label_block (K, S)."""
         if new_samples is not None:
-            if new_samples.shape != self.inputs.shape or new_samples.dtype != torch.float32 \
+            if new_samples.shape != self.inputs.shape or new_samples.dtype != self.input_dtype \
                     or not new_samples.is_cuda:
-                raise ValueError(f"new_samples must be a CUDA float32 tensor of shape {tuple(self.inputs.shape)}")
+                raise ValueError(f"new_samples must be a CUDA {self._dtype_name} tensor of shape "
+                                 f"{tuple(self.inputs.shape)}")
             if (self.graph is None or self.graph_host_io) and self.kernel == "hop" and new_samples.stride(2) == 1 \
                     and hop_rows_disjoint(self.n, self.K, new_samples.stride(0), new_samples.stride(1), self.cfg.hop):
                 self._hop_call(new_samples, self.K, self.label_block)  # read in place
@@ -193,10 +224,10 @@ class StreamBatch:
         return self.label_block
 
     def attach_host_io(self):
-        """Pinned host buffers for step_host: host_inputs (K, S, hop) fp32,
-        host_labels (K, S) uint8."""
+        """Pinned host buffers for step_host: host_inputs (K, S, hop) of the
+        batch's input dtype, host_labels (K, S) uint8."""
         if self.host_inputs is None:
-            self.host_inputs = torch.zeros(tuple(self.inputs.shape), dtype=torch.float32, pin_memory=True)
+            self.host_inputs = torch.zeros(tuple(self.inputs.shape), dtype=self.input_dtype, pin_memory=True)
             self.host_labels = torch.full(tuple(self.label_block.shape), 255, dtype=torch.uint8,
                                           pin_memory=True)
         return self.host_inputs, self.host_labels
@@ -268,6 +299,13 @@ class StreamBatch:
         self.graph_host_io = bool(host_io)
         return g
 
+    def host_pipeline(self, depth=2):
+        """A HostPipeline over this batch: `depth` blocks of K hops in flight
+        (H2D, kernel(s), D2H on three streams).  Launches are direct, not a
+        graph; use either the pipeline or step()/step_block()/step_host()
+        between two synchronisations, not both at once."""
+        return HostPipeline(self, depth)
+
     @property
     def graph_direct(self):
         """True when replays dispatch the captured graph's single kernel node."""
@@ -278,3 +316,104 @@ class StreamBatch:
         if fin is not None:
             fin()  # the plan before the graph it points into
         self._graph_plan = None
+
+
+class HostPipeline:
+    """`depth` blocks of a StreamBatch in flight between pinned host memory
+    and the device (StreamBatch.host_pipeline).
+
+    Slot d has pinned ``host_inputs[d]`` (K, S, hop; the batch's input dtype)
+    and ``host_labels[d]`` (K, S; uint8), and a device input block and a device
+    label block of its own.  submit(d) enqueues
+      the H2D copy of host_inputs[d] on the copy-in stream, after slot d's
+        previous kernel has finished with the device input block;
+      the hop kernel(s) on the compute stream, after that copy and after slot
+        d's previous D2H copy has read the device label block;
+      the D2H copy into host_labels[d] on the copy-out stream, after the kernel.
+    Every submit's kernels go to the one compute stream, in submit order, so
+    the streams' state (frames, ring, count) advances exactly as in serial
+    steps; a depth of 1 is the serial order.  wait(d) blocks the host until
+    slot d's D2H copy has landed and returns host_labels[d]; after it the
+    producer may rewrite host_inputs[d].  The batch's own ``inputs`` /
+    ``label_block`` / ``labels`` are not touched.
+    """
+
+    def __init__(self, batch, depth=2):
+        depth = int(depth)
+        if depth < 1:
+            raise ValueError("depth must be >= 1")
+        if batch.graph is not None:
+            raise ValueError("a captured batch replays its graph; the pipeline launches directly")
+        self.batch, self.depth = batch, depth
+        dev = batch.frames.device
+        ishape, lshape = tuple(batch.inputs.shape), tuple(batch.label_block.shape)
+        self.host_inputs = [torch.zeros(ishape, dtype=batch.input_dtype, pin_memory=True) for _ in range(depth)]
+        self.host_labels = [torch.full(lshape, 255, dtype=torch.uint8, pin_memory=True) for _ in range(depth)]
+        self._dev_in = [torch.zeros(ishape, dtype=batch.input_dtype, device=dev) for _ in range(depth)]
+        self._dev_lab = [torch.full(lshape, 255, dtype=torch.uint8, device=dev) for _ in range(depth)]
+        self.copy_in, self.compute, self.copy_out = (torch.cuda.Stream(device=dev) for _ in range(3))
+        self._run_ptr = ctypes.c_void_p(self.compute.cuda_stream)
+        self._h2d = [torch.cuda.Event() for _ in range(depth)]
+        self._ran = [torch.cuda.Event() for _ in range(depth)]
+        self._d2h = [torch.cuda.Event() for _ in range(depth)]
+        self._busy = [False] * depth
+        self._used = [False] * depth
+        self._in_flight = 0
+        cur = torch.cuda.current_stream(dev)
+        for s in (self.copy_in, self.compute, self.copy_out):  # after the fills above
+            s.wait_stream(cur)
+
+    def submit(self, d):
+        """Enqueue slot d's block (host_inputs[d] -> host_labels[d]); returns
+        at once.  A slot submitted and not yet waited raises ValueError."""
+        if not 0 <= d < self.depth:
+            raise ValueError(f"slot must be in [0, {self.depth})")
+        if self._busy[d]:
+            raise ValueError(f"slot {d} was submitted and not waited")
+        b = self.batch
+        cur = torch.cuda.current_stream(b.frames.device)
+        if self._in_flight == 0:  # idle: whatever the caller did to the state (prime, reset, steps) comes first
+            self.compute.wait_stream(cur)
+        used = self._used[d]
+        try:
+            if used:
+                self.copy_in.wait_event(self._ran[d])
+            torch.cuda.set_stream(self.copy_in)
+            self._dev_in[d].copy_(self.host_inputs[d], non_blocking=True)
+            self._h2d[d].record(self.copy_in)
+            self.compute.wait_event(self._h2d[d])
+            if used:
+                self.compute.wait_event(self._d2h[d])
+            if b.kernel == "hop":
+                b._hop_call(self._dev_in[d], b.K, self._dev_lab[d], self._run_ptr)
+            else:
+                for k in range(b.K):
+                    b._three(self._dev_in[d][k], self._dev_lab[d][k], self._run_ptr)
+            self._ran[d].record(self.compute)
+            self.copy_out.wait_event(self._ran[d])
+            torch.cuda.set_stream(self.copy_out)
+            self.host_labels[d].copy_(self._dev_lab[d], non_blocking=True)
+            self._d2h[d].record(self.copy_out)
+        finally:
+            torch.cuda.set_stream(cur)
+        self._busy[d] = True
+        self._used[d] = True
+        self._in_flight += 1
+
+    def wait(self, d):
+        """Block the host until slot d's labels are in host_labels[d]
+        (returned).  Only the slot's D2H event is waited on."""
+        if not 0 <= d < self.depth or not self._busy[d]:
+            raise ValueError(f"slot {d} has no block in flight")
+        self._d2h[d].synchronize()
+        self._busy[d] = False
+        self._in_flight -= 1
+        return self.host_labels[d]
+
+    def drain(self):
+        """wait() on every slot in flight; the current stream then sees the
+        batch's state as the last kernel left it."""
+        for d in range(self.depth):
+            if self._busy[d]:
+                self.wait(d)
+        torch.cuda.current_stream(self.batch.frames.device).wait_stream(self.compute)
