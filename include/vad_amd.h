@@ -357,6 +357,73 @@ int32_t vad_graph_plan_direct(const vad_graph_plan* plan);
 int vad_graph_plan_destroy(vad_graph_plan* plan);
 
 /* ---------------------------------------------------------------------------
+ * Speech segments and voiced audio from clip labels: what vad.py:52-57,67-72
+ * does on the host with the frames the analyser returned as active
+ * (active_frames += np_frame.tobytes(), written out as a wav), here on the
+ * device, from the per-window labels of the clip path.
+ *   a[i] = (labels[i] == active), i < n; window i stands for frame i + 2, the
+ *   samples [(i+2)*hop, (i+2)*hop + frame_size) (Row i above;
+ *   sklearn_analyser.py:19,52,77).
+ *   close(g): every maximal run of a == 0 of length <= g with an active
+ *     window on both sides becomes 1 (a run touching an end never closes);
+ *   open(m): every maximal run of a == 1 shorter than m becomes 0 (runs at
+ *     the ends included);
+ *   smooth(max_gap, min_run) = close(max_gap), then open(min_run); both in
+ *     windows, 0 = off, any value works.
+ * The scans run on tiles of VAD_SEG_TILE labels; one pass of the tile-total
+ * scan covers VAD_SEG_CARRY_PASS tiles (more tiles: more passes of its one
+ * workgroup).  `ws` is a device workspace of >= vad_segments_workspace_bytes(n)
+ * bytes, 16-byte aligned (may be NULL for n == 0).
+ * ------------------------------------------------------------------------- */
+#define VAD_SEG_TILE 1024
+#define VAD_SEG_CARRY_PASS 256
+size_t vad_segments_workspace_bytes(int64_t n_labels);
+
+/* out[i] = smooth(max_gap, min_run)(a)[i] as uint8 0 / 1.  out must not
+ * overlap labels (VAD_EINVAL). */
+int vad_label_smooth(const uint8_t* labels, int64_t n, int32_t active, int64_t max_gap, int64_t min_run,
+                     uint8_t* out, void* ws, size_t ws_bytes, void* stream);
+
+/* Segments in samples.  After smooth(max_gap, min_run), close(frame_size /
+ * hop - 1) joins runs whose frame ranges overlap or touch; each remaining run
+ * [i0, i1] is row k of `segments`, three int64:
+ *   start = (i0+2)*hop, end = min((i1+2)*hop + frame_size, n_samples),
+ *   offset = sum of end - start over the rows before it (its place in the
+ *   packed output of vad_gather_segments_*).
+ * Rows are ascending, disjoint and non-touching.  counts[0] = rows found,
+ * counts[1] = voiced samples of all rows found; only the first `capacity`
+ * rows are written.  VAD_EINVAL unless 0 < hop <= frame_size and
+ * n <= vad_n_frames(n_samples, frame_size, hop) - 5. */
+int vad_label_segments(const uint8_t* labels, int64_t n, int32_t active, int64_t max_gap, int64_t min_run,
+                       int32_t frame_size, int32_t hop, int64_t n_samples,
+                       int64_t* segments /* capacity x 3 */, int64_t capacity, int64_t* counts /* 2 */,
+                       void* ws, size_t ws_bytes, void* stream);
+
+/* out = the concatenation of audio[start_k : end_k] over the rows written
+ * (min(counts[0], capacity) of them), bits copied; writing stops at
+ * out_capacity elements and nothing past the voiced count is touched.  out
+ * must not overlap audio. */
+int vad_gather_segments_f32(const float* audio, int64_t n_samples, const int64_t* segments, const int64_t* counts,
+                            int64_t capacity, float* out, int64_t out_capacity, void* stream);
+int vad_gather_segments_i16(const int16_t* audio, int64_t n_samples, const int64_t* segments, const int64_t* counts,
+                            int64_t capacity, int16_t* out, int64_t out_capacity, void* stream);
+
+/* The form vad.py itself writes: out[r*frame_size + t] = audio[(i_r+2)*hop + t]
+ * for the r-th window with labels[i] == active (overlapping samples repeat,
+ * as the reference's byte concatenation repeats them).  Any hop > 0 (hop ==
+ * frame_size: the recorder's framing); the last window's frame must end
+ * inside the clip.  *count = windows found; rows >= out_capacity_frames are
+ * not written. */
+int vad_gather_active_frames_f32(const float* audio, int64_t n_samples, const uint8_t* labels, int64_t n,
+                                 int32_t active, int32_t frame_size, int32_t hop, float* out,
+                                 int64_t out_capacity_frames, int64_t* count, void* ws, size_t ws_bytes,
+                                 void* stream);
+int vad_gather_active_frames_i16(const int16_t* audio, int64_t n_samples, const uint8_t* labels, int64_t n,
+                                 int32_t active, int32_t frame_size, int32_t hop, int16_t* out,
+                                 int64_t out_capacity_frames, int64_t* count, void* ws, size_t ws_bytes,
+                                 void* stream);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU clip sharding: one process per GPU, each
  * classifying its shard (vad_amd/dist.py split_clip: windows [w_lo, w_hi)
  * from samples [160 w_lo, 160 (w_hi + 4) + 401)), then ONE collective: the

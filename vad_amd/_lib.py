@@ -84,6 +84,16 @@ SIGNATURES = {
     "vad_graph_plan_launch": (c_int, [c_vp, c_vp]),
     "vad_graph_plan_direct": (c_i32, [c_vp]),
     "vad_graph_plan_destroy": (c_int, [c_vp]),
+    "vad_segments_workspace_bytes": (c_sz, [c_i64]),
+    "vad_label_smooth": (c_int, [c_vp, c_i64, c_i32, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "vad_label_segments": (c_int, [c_vp, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                   c_sz, c_vp]),
+    "vad_gather_segments_f32": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "vad_gather_segments_i16": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "vad_gather_active_frames_f32": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp,
+                                             c_sz, c_vp]),
+    "vad_gather_active_frames_i16": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp,
+                                             c_sz, c_vp]),
     "vad_rccl_available": (c_int, []),
     "vad_rccl_error_string": (ctypes.c_char_p, []),
     "vad_rccl_unique_id": (c_int, [c_vp]),

@@ -121,6 +121,28 @@ class VadPipeline:
             _lib.ptr(ws), 0 if ws is None else ws.numel(), _lib.stream_ptr(stream)), fn)
         return out
 
+    def segments(self, audio, max_gap=0, min_run=0, active=1, capacity=None, stream=None):
+        """Speech segments of a device clip: labels(), then
+        vad_amd.segments.label_segments at the pipeline's framing (max_gap /
+        min_run in windows).  Returns a Segments; no synchronisation."""
+        from .segments import label_segments
+        labels = self.labels(audio, stream=stream)
+        return label_segments(labels, audio.numel(), self.cfg.frame_size, self.cfg.hop, max_gap=max_gap,
+                              min_run=min_run, active=active, capacity=capacity, stream=stream)
+
+    def voiced(self, audio, max_gap=0, min_run=0, active=1, stream=None):
+        """The voiced samples of a device clip (float32 or int16, bits
+        copied), packed in order: segments(), then the device gather.  The
+        result is trimmed to the voiced count, which lives on the device, so
+        this call synchronises once (vad_amd.segments.voiced_audio is the form
+        that does not)."""
+        from .segments import voiced_audio
+        seg = self.segments(audio, max_gap=max_gap, min_run=min_run, active=active, stream=stream)
+        out, counts = voiced_audio(audio, seg, stream=stream)
+        if stream is not None:
+            stream.synchronize()
+        return out[:int(counts[1].item())]
+
     def process_clip(self, data):
         """process_file's feature list for an in-memory clip: (F-5, 3, n_mfcc) float64
         (unnormalised, file_processing.py:40-70)."""
