@@ -424,6 +424,108 @@ int vad_gather_active_frames_i16(const int16_t* audio, int64_t n_samples, const 
                                  void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Streaming segments: the same segments and voiced samples, online, for the
+ * S streams of the hop kernels above (vad.py:32-59 keeps the samples of the
+ * active frames while it feeds them).  Per stream the entries consume the
+ * label blocks vad_stream_hops writes and, optionally, the same hop sample
+ * blocks; with a fixed delay they append finished segments to a per-stream
+ * table and emit the voiced samples.  One kernel per call, one wave per
+ * stream; capturable after the hop kernel on the same stream, no host step.
+ *
+ * Equivalent clip of a stream (L = frame_size, H = hop, 0 < H <= L): the
+ *   L - H carried samples (zeros, or what the host carried over) followed by
+ *   every hop pushed since; T hops make L - H + T*H samples, hop t (0-based)
+ *   sits at [L-H + t*H, L-H + (t+1)*H).  The label byte of hop t >= 5 is
+ *   window t - 5 of that clip (any byte != active is inactive); the label
+ *   bytes of hops t < 5 are ignored, whatever they hold.
+ * Final mask: c = close(j)(open(min_run)(close(max_gap)(a))), j = L / H - 1,
+ *   the mask whose runs vad_label_segments turns into rows.  Its rules at the
+ *   end of a sequence equal "inactive windows follow forever", so a stream
+ *   cut off anywhere and flushed gives the offline result on its labels.
+ * Delay: D = max_gap + max(min_run, 1) + j + 1 windows (vad_stream_seg_delay;
+ *   -1 for bad arguments: hop outside (0, frame_size], a negative value, or
+ *   max_gap / min_run above 2^29).  c[i] is the same for every continuation
+ *   once the labels up to window i + D are known.
+ * Hop t decides window d = t - 5 - D (nothing while d < 0) and the slab
+ *   [(d+2)H, (d+3)H) of the clip.  Every segment starts on a multiple of H,
+ *   so the voiced part of a slab is a prefix, of length
+ *   clamp((e+2)H + L - (d+2)H, 0, H) with e the last window <= d with c = 1
+ *   (0 when there is none).  Row (k, s) of `voiced` gets that prefix of hop k
+ *   of the block, copied bit for bit from the stream's samples, and
+ *   voiced_len[k, s] its length; elements past the prefix are not touched.
+ *   The prefixes of a stream, in order, are its packed voiced audio.
+ * Segments: a run [i0, i1] of c is appended by the hop whose d is i1 + 1
+ *   (the run is complete, the window after it decided and inactive), as the
+ *   int64 pair start = (i0+2)H, end = (i1+2)H + L (inside the clip: the last
+ *   window's frame ends in it).  found[s] counts every segment appended;
+ *   only the first `capacity` rows of stream s are written; rows ascend.
+ * State: vad_stream_seg_state_bytes(S) bytes, 8-byte aligned; ALL ZERO is a
+ *   stream before its first hop, with found[s] = 0 (and a zeroed history
+ *   slice when no carry is wanted).  The caller passes the same max_gap,
+ *   min_run, frame_size, hop, history and history_elems on every call.
+ * History: the entries with audio keep their own copy of the samples (the
+ *   caller's hop blocks are recycled) in `history`, history_elems elements of
+ *   the sample type, stream s owning [s*R, (s+1)*R), R = history_elems / S >=
+ *   (D+3)H + L + n_hops*H (vad_stream_seg_history_elems gives S times that
+ *   for the largest block; R <= 2^30).  Clip position p lives at index
+ *   (p - (L-H)) mod R of the slice, so the carried samples, when they matter
+ *   (L > 3H: positions in [2H, L-H) can be voiced), go to its last L - H
+ *   elements before the first hop.
+ * Flush: vad_stream_seg_flush_rows = D + 2 + ceil(L / H) more hops of
+ *   inactive windows without samples: every window is decided, the open
+ *   segment is appended, the remaining prefixes are emitted (F rows of
+ *   voiced / voiced_len; positions past the clip's end are never voiced).
+ *   After it every stream of the call equals vad_label_segments /
+ *   vad_gather_segments_* on its equivalent clip.  CONTRACT: a flushed state
+ *   is ended -- further hops and flushes emit empty rows and change nothing
+ *   -- until the host zeroes it (state slice, found[s], and the history slice
+ *   or its carry): zeroing one stream's slices restarts that stream alone,
+ *   together with its ring / count of the hop kernel.
+ * VAD_EINVAL: hop outside (0, frame_size]; a negative max_gap, min_run,
+ *   capacity, n_streams or n_hops; active outside [0, 255) (255 is the "no
+ *   label yet" byte); a NULL pointer that would be used; n_hops > 1 with
+ *   label_block_stride < n_streams; hop_stride < hop, or hop rows refused by
+ *   vad_stream_hops (the same layouts are read in place, any element
+ *   offset); a history too small (or R > 2^30); misaligned pointers.
+ *   n_streams == 0 or n_hops == 0: nothing is done, VAD_OK.
+ * ------------------------------------------------------------------------- */
+int64_t vad_stream_seg_delay(int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop);
+int64_t vad_stream_seg_flush_rows(int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop);
+size_t vad_stream_seg_state_bytes(int64_t n_streams);
+int64_t vad_stream_seg_history_elems(int64_t n_streams, int32_t n_hops_max, int64_t max_gap, int64_t min_run,
+                                     int32_t frame_size, int32_t hop);
+/* Events only: segments and found, no audio, no history. */
+int vad_stream_segments(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams, int32_t n_hops,
+                        int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                        void* state, int64_t* segments /* S x capacity x 2 */, int64_t capacity,
+                        int64_t* found /* S */, void* stream);
+/* The same plus the hop block vad_stream_hops / _i16 read (hop k's row s at
+ * hop_samples + k * hop_block_stride + s * hop_stride) and the voiced rows. */
+int vad_stream_segments_f32(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams, int32_t n_hops,
+                            int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                            void* state, int64_t* segments, int64_t capacity, int64_t* found,
+                            const float* hop_samples, int64_t hop_stride, int64_t hop_block_stride, float* history,
+                            int64_t history_elems, float* voiced /* n_hops x S x hop */,
+                            int32_t* voiced_len /* n_hops x S */, void* stream);
+int vad_stream_segments_i16(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams, int32_t n_hops,
+                            int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                            void* state, int64_t* segments, int64_t capacity, int64_t* found,
+                            const int16_t* hop_samples, int64_t hop_stride, int64_t hop_block_stride,
+                            int16_t* history, int64_t history_elems, int16_t* voiced, int32_t* voiced_len,
+                            void* stream);
+/* Flush (see above); voiced is F x S x hop, voiced_len F x S, F = vad_stream_seg_flush_rows. */
+int vad_stream_segments_flush(int64_t n_streams, int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                              void* state, int64_t* segments, int64_t capacity, int64_t* found, void* stream);
+int vad_stream_segments_flush_f32(int64_t n_streams, int64_t max_gap, int64_t min_run, int32_t frame_size,
+                                  int32_t hop, void* state, int64_t* segments, int64_t capacity, int64_t* found,
+                                  float* history, int64_t history_elems, float* voiced, int32_t* voiced_len,
+                                  void* stream);
+int vad_stream_segments_flush_i16(int64_t n_streams, int64_t max_gap, int64_t min_run, int32_t frame_size,
+                                  int32_t hop, void* state, int64_t* segments, int64_t capacity, int64_t* found,
+                                  int16_t* history, int64_t history_elems, int16_t* voiced, int32_t* voiced_len,
+                                  void* stream);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU clip sharding: one process per GPU, each
  * classifying its shard (vad_amd/dist.py split_clip: windows [w_lo, w_hi)
  * from samples [160 w_lo, 160 (w_hi + 4) + 401)), then ONE collective: the

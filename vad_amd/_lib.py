@@ -94,6 +94,21 @@ SIGNATURES = {
                                              c_sz, c_vp]),
     "vad_gather_active_frames_i16": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp,
                                              c_sz, c_vp]),
+    "vad_stream_seg_delay": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
+    "vad_stream_seg_flush_rows": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
+    "vad_stream_seg_state_bytes": (c_sz, [c_i64]),
+    "vad_stream_seg_history_elems": (c_i64, [c_i64, c_i32, c_i64, c_i64, c_i32, c_i32]),
+    "vad_stream_segments": (c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64,
+                                    c_vp, c_vp]),
+    "vad_stream_segments_f32": (c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp,
+                                        c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "vad_stream_segments_i16": (c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp,
+                                        c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "vad_stream_segments_flush": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "vad_stream_segments_flush_f32": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp,
+                                              c_i64, c_vp, c_vp, c_vp]),
+    "vad_stream_segments_flush_i16": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp,
+                                              c_i64, c_vp, c_vp, c_vp]),
     "vad_rccl_available": (c_int, []),
     "vad_rccl_error_string": (ctypes.c_char_p, []),
     "vad_rccl_unique_id": (c_int, [c_vp]),

@@ -972,6 +972,143 @@ int vad_stream_step(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, const fl
                                 labels, st);
 }
 
+// ---------------------------------------------------------------------------
+// Streaming segments (stream_segments_kernel.hip)
+// ---------------------------------------------------------------------------
+constexpr int64_t kSegParamMax = (int64_t)1 << 29;  // max_gap, min_run: the flush row count stays an int32
+constexpr int64_t kSegRingMax = (int64_t)1 << 30;   // history elements per stream: ring indices stay an int32
+
+int64_t vad_stream_seg_delay(int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop) {
+  if (max_gap < 0 || min_run < 0 || max_gap > kSegParamMax || min_run > kSegParamMax) return -1;
+  if (frame_size <= 0 || hop <= 0 || hop > frame_size) return -1;
+  return max_gap + (min_run > 1 ? min_run : 1) + (frame_size / hop - 1) + 1;
+}
+
+int64_t vad_stream_seg_flush_rows(int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop) {
+  const int64_t d = vad_stream_seg_delay(max_gap, min_run, frame_size, hop);
+  return d < 0 ? -1 : d + 2 + (frame_size + hop - 1) / hop;
+}
+
+size_t vad_stream_seg_state_bytes(int64_t n_streams) {
+  return n_streams > 0 ? (size_t)n_streams * kSegStreamStateBytes : 0;
+}
+
+// history elements one stream needs for blocks of n_hops hops (-1: bad arguments or past kSegRingMax)
+static int64_t seg_ring_need(int64_t n_hops, int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop) {
+  const int64_t d = vad_stream_seg_delay(max_gap, min_run, frame_size, hop);
+  if (d < 0 || n_hops < 0) return -1;
+  const int64_t need = (d + 3 + n_hops) * hop + frame_size;
+  return need > kSegRingMax ? -1 : need;
+}
+
+int64_t vad_stream_seg_history_elems(int64_t n_streams, int32_t n_hops_max, int64_t max_gap, int64_t min_run,
+                                     int32_t frame_size, int32_t hop) {
+  const int64_t need = seg_ring_need(n_hops_max, max_gap, min_run, frame_size, hop);
+  if (need < 0 || n_streams < 0 || n_streams > INT32_MAX) return -1;
+  return n_streams * need;
+}
+
+// One body for the six entries: labels == NULL with flush set is a flush of
+// vad_stream_seg_flush_rows hops; audio_bytes 0 is the events-only form.
+// Every check comes before any HIP call, in the same order for every form.
+static int stream_segments_entry(bool flush, const uint8_t* labels, int64_t label_block_stride, int64_t n_streams,
+                                 int64_t n_hops, int32_t active, int64_t max_gap, int64_t min_run,
+                                 int32_t frame_size, int32_t hop, void* state, int64_t* segments, int64_t capacity,
+                                 int64_t* found, int audio_bytes, const void* hop_samples, int64_t hop_stride,
+                                 int64_t hop_block_stride, void* history, int64_t history_elems, void* voiced,
+                                 int32_t* voiced_len, void* stream) {
+  const int64_t delay = vad_stream_seg_delay(max_gap, min_run, frame_size, hop);
+  if (delay < 0) return VAD_EINVAL;  // hop outside (0, frame_size], a negative gap or run
+  if (n_streams < 0 || n_streams > INT32_MAX || n_hops < 0 || n_hops > INT32_MAX || capacity < 0)
+    return VAD_EINVAL;
+  if (active < 0 || active >= 255) return VAD_EINVAL;  // 255 is "no label yet"
+  if (!flush && n_hops > 1 && label_block_stride < n_streams) return VAD_EINVAL;
+  if (audio_bytes && !flush) {
+    if (hop_stride < hop) return VAD_EINVAL;
+    if (n_hops > 1 && !vad_hop_layout_disjoint(n_streams, (int32_t)n_hops, hop_block_stride, hop_stride, hop))
+      return VAD_EINVAL;
+  }
+  if (audio_bytes && history_elems < 0) return VAD_EINVAL;
+  if (n_streams == 0 || n_hops == 0) return VAD_OK;
+  if ((!flush && !labels) || !state || !found || (capacity > 0 && !segments)) return VAD_EINVAL;
+  if (capacity > INT64_MAX / 2 / n_streams) return VAD_EINVAL;
+  if (reinterpret_cast<uintptr_t>(state) % 8 || reinterpret_cast<uintptr_t>(segments) % 8 ||
+      reinterpret_cast<uintptr_t>(found) % 8)
+    return VAD_EINVAL;
+  SegStreamArgs a{};
+  if (audio_bytes) {
+    if ((!flush && !hop_samples) || !history || !voiced || !voiced_len) return VAD_EINVAL;
+    if (reinterpret_cast<uintptr_t>(hop_samples) % audio_bytes || reinterpret_cast<uintptr_t>(history) % audio_bytes ||
+        reinterpret_cast<uintptr_t>(voiced) % audio_bytes || reinterpret_cast<uintptr_t>(voiced_len) % 4)
+      return VAD_EINVAL;
+    const int64_t need = seg_ring_need(flush ? 0 : n_hops, max_gap, min_run, frame_size, hop);
+    const int64_t ring = history_elems / n_streams;
+    if (need < 0 || ring < need || ring > kSegRingMax) return VAD_EINVAL;
+    a.hop_samples = hop_samples, a.hstride = hop_stride, a.hop_kstride = hop_block_stride;
+    a.history = history, a.ring = (int)ring, a.voiced = voiced, a.voiced_len = voiced_len;
+  }
+  a.labels = flush ? nullptr : labels, a.lab_kstride = label_block_stride;
+  a.n_streams = n_streams, a.n_hops = (int)n_hops, a.active = active;
+  a.max_gap = max_gap, a.min_run = min_run, a.join = frame_size / hop - 1, a.delay = delay;
+  a.frame_size = frame_size, a.hop = hop;
+  a.state = state, a.segments = segments, a.capacity = capacity, a.found = found;
+  return (int)launch_stream_segments(a, audio_bytes, (hipStream_t)stream);
+}
+
+int vad_stream_segments(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams, int32_t n_hops,
+                        int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                        void* state, int64_t* segments, int64_t capacity, int64_t* found, void* stream) {
+  return stream_segments_entry(false, labels, label_block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 0, nullptr, 0, 0, nullptr, 0,
+                               nullptr, nullptr, stream);
+}
+
+int vad_stream_segments_f32(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams, int32_t n_hops,
+                            int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                            void* state, int64_t* segments, int64_t capacity, int64_t* found,
+                            const float* hop_samples, int64_t hop_stride, int64_t hop_block_stride, float* history,
+                            int64_t history_elems, float* voiced, int32_t* voiced_len, void* stream) {
+  return stream_segments_entry(false, labels, label_block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 4, hop_samples, hop_stride,
+                               hop_block_stride, history, history_elems, voiced, voiced_len, stream);
+}
+
+int vad_stream_segments_i16(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams, int32_t n_hops,
+                            int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                            void* state, int64_t* segments, int64_t capacity, int64_t* found,
+                            const int16_t* hop_samples, int64_t hop_stride, int64_t hop_block_stride,
+                            int16_t* history, int64_t history_elems, int16_t* voiced, int32_t* voiced_len,
+                            void* stream) {
+  return stream_segments_entry(false, labels, label_block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 2, hop_samples, hop_stride,
+                               hop_block_stride, history, history_elems, voiced, voiced_len, stream);
+}
+
+int vad_stream_segments_flush(int64_t n_streams, int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                              void* state, int64_t* segments, int64_t capacity, int64_t* found, void* stream) {
+  return stream_segments_entry(true, nullptr, 0, n_streams, vad_stream_seg_flush_rows(max_gap, min_run, frame_size, hop),
+                               1, max_gap, min_run, frame_size, hop, state, segments, capacity, found, 0, nullptr,
+                               0, 0, nullptr, 0, nullptr, nullptr, stream);
+}
+
+int vad_stream_segments_flush_f32(int64_t n_streams, int64_t max_gap, int64_t min_run, int32_t frame_size,
+                                  int32_t hop, void* state, int64_t* segments, int64_t capacity, int64_t* found,
+                                  float* history, int64_t history_elems, float* voiced, int32_t* voiced_len,
+                                  void* stream) {
+  return stream_segments_entry(true, nullptr, 0, n_streams, vad_stream_seg_flush_rows(max_gap, min_run, frame_size, hop),
+                               1, max_gap, min_run, frame_size, hop, state, segments, capacity, found, 4, nullptr,
+                               0, 0, history, history_elems, voiced, voiced_len, stream);
+}
+
+int vad_stream_segments_flush_i16(int64_t n_streams, int64_t max_gap, int64_t min_run, int32_t frame_size,
+                                  int32_t hop, void* state, int64_t* segments, int64_t capacity, int64_t* found,
+                                  int16_t* history, int64_t history_elems, int16_t* voiced, int32_t* voiced_len,
+                                  void* stream) {
+  return stream_segments_entry(true, nullptr, 0, n_streams, vad_stream_seg_flush_rows(max_gap, min_run, frame_size, hop),
+                               1, max_gap, min_run, frame_size, hop, state, segments, capacity, found, 2, nullptr,
+                               0, 0, history, history_elems, voiced, voiced_len, stream);
+}
+
 // Replay of a captured graph (a hop block with its host copies,
 // vad_amd.stream.StreamBatch.capture): hipGraphLaunch on the caller's stream.
 int vad_graph_launch(void* graph_exec, void* stream) {

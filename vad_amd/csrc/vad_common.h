@@ -154,6 +154,31 @@ hipError_t launch_stream_push(float* frames, int64_t fstride, int len, const voi
                               int64_t hstride, int hlen, int64_t n_streams, hipStream_t st);
 hipError_t launch_preemphasis(const float* x, float* y, int64_t n_rows, int64_t row_len, int64_t stride, float a,
                               hipStream_t st);
+// Streaming segments (stream_segments_kernel.hip): n_hops hops of every
+// stream through the segmenter, or n_hops flush hops (labels == nullptr).
+// audio_bytes 0: events only (no hop, history, voiced); 4 / 2: fp32 / int16
+// samples, strides in elements.  The C entries have checked everything.
+constexpr size_t kSegStreamStateBytes = 128;  // per stream; all zero = a stream before its first hop
+struct SegStreamArgs {
+  const uint8_t* labels;  // nullptr: flush (inactive windows, no new samples; the state ends)
+  int64_t lab_kstride;
+  int64_t n_streams;
+  int n_hops;
+  int active;
+  int64_t max_gap, min_run, join, delay;  // join = frame_size / hop - 1; delay = D
+  int frame_size, hop;
+  void* state;
+  int64_t* segments;
+  int64_t capacity;
+  int64_t* found;
+  const void* hop_samples;
+  int64_t hstride, hop_kstride;
+  void* history;
+  int ring;  // history elements per stream, <= 2^30
+  void* voiced;
+  int32_t* voiced_len;
+};
+hipError_t launch_stream_segments(const SegStreamArgs& a, int audio_bytes, hipStream_t st);
 // any fft_n other than 512 (spec_generic.hip): mode 0 frames -> MFCC,
 // 1 frames -> spectra, 2 spectra -> MFCC; tw = exp(-2 pi i m / fft_n), fp64
 hipError_t launch_generic(int mode, const MfccDev* plan, const float* src, int64_t stride, int len, int64_t n,

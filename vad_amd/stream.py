@@ -306,6 +306,15 @@ class StreamBatch:
         between two synchronisations, not both at once."""
         return HostPipeline(self, depth)
 
+    def segmenter(self, **kw):
+        """A StreamSegmenter (vad_amd.stream_segments) matching this batch's
+        streams, framing, hops per step and input dtype; kw: max_gap, min_run,
+        active, capacity.  Feed it ``label_block`` and ``inputs`` (or the
+        blocks step_block read in place) after each step."""
+        from .stream_segments import StreamSegmenter
+        return StreamSegmenter(self.n, self.cfg, hops_per_step=self.K, audio_dtype=self.input_dtype,
+                               device=self.frames.device, **kw)
+
     @property
     def graph_direct(self):
         """True when replays dispatch the captured graph's single kernel node."""
