@@ -207,6 +207,63 @@ int vad_mfcc_ffn_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, const i
                      uint8_t* labels, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * FFN training (reference learning/ffn_trainer.py:118-154: Keras
+ * optimizer='adadelta', loss='categorical_crossentropy', train_on_batch):
+ * many models per launch, one workgroup per model, the model's state in LDS
+ * for all the steps of a launch.
+ *
+ * A model's state block is 3 * count floats, count =
+ * vad_ffn_train_param_count(): [params | E[g^2] | E[dx^2]], each section
+ * W0 (in, out) row-major, b0, W1, b1, ...  Zero accumulators = a fresh model.
+ * Model m's block starts at state + m * 3 * count.
+ *
+ * One step on rows r < batch of x[order[step * batch + r]] (x: n_rows rows of
+ * dims[0] floats, y: their class indices): forward with ReLU between layers
+ * and a max-subtracted softmax, loss = -mean(log p[label]), gradient
+ * (p - onehot) / batch back through the layers, then Adadelta (Keras 1 /
+ * torch.optim.Adadelta) on every parameter:
+ *   a = rho a + (1 - rho) g^2;  u = g sqrt(d + eps) / sqrt(a + eps);
+ *   p -= lr u;  d = rho d + (1 - rho) u^2.
+ * The softmax output is not clipped before the log (Keras clips it to
+ * [1e-7, 1 - 1e-7]).  GEMMs: v_mfma_f32_16x16x4_f32, everything else fp32 in
+ * a fixed order; a run is bit-reproducible, and a model's result does not
+ * depend on the other models of the launch.
+ *
+ * Shapes: those of vad_ffn_plan_create (1..4 layers, every dim 1..64, classes
+ * <= 4), batch 1..64.  LDS budget: 4 bytes x (3 count, rounded up to 4,
+ *   + bp * (2 (pad16(dims[0]) + 2) + sum_{l=1..L-1} (pad16(dims[l]) + 2)
+ *           + sum_{l=1..L} (pad16(dims[l]) + 2)) + 128)  <=  160 KiB,
+ * bp = batch rounded up to 16, pad16 = rounded up to 16; VAD_EUNSUPPORTED
+ * past it.  39-64-32-16-3 and 13-64-64-2 fit at every batch.
+ * ------------------------------------------------------------------------- */
+#define VAD_TRAIN_EVAL_CHUNK_ROWS 1024
+
+/* Parameters of one model; -1 for shapes outside the limits above. */
+int64_t vad_ffn_train_param_count(int32_t n_layers, const int32_t* dims /* n_layers+1 */);
+
+/* n_steps consecutive steps of n_models models.  order: n_steps * batch row
+ * indices per model, model m's at order + m * order_model_stride (0: every
+ * model runs the same order).  The caller guarantees 0 <= order[i] < n_rows
+ * and y[i] < dims[n_layers]; neither is checked on the device (a label is
+ * only ever compared, an index is an address).  hyper: (lr, rho, eps) per
+ * model.  step_loss (may be NULL): step_loss[m * n_steps + k] = the loss of
+ * step k before its update. */
+int vad_ffn_train_steps(int32_t n_layers, const int32_t* dims, float* state, int64_t n_models,
+                        const float* x, const uint8_t* y, int64_t n_rows, const int32_t* order,
+                        int64_t order_model_stride, int32_t batch, int64_t n_steps,
+                        const float* hyper, float* step_loss, void* stream);
+
+/* model.evaluate_generator (ffn_trainer.py:154).  Rows are taken in chunks
+ * of VAD_TRAIN_EVAL_CHUNK_ROWS: n_chunks = vad_ffn_train_eval_chunks(n_rows)
+ * (-1 for n_rows < 0); loss_sums[m * n_chunks + c] = the summed loss (fp32)
+ * and correct[m * n_chunks + c] = the rows whose first-max argmax equals the
+ * label, of chunk c under model m.  The caller adds the chunks. */
+int64_t vad_ffn_train_eval_chunks(int64_t n_rows);
+int vad_ffn_train_eval(int32_t n_layers, const int32_t* dims, const float* state, int64_t n_models,
+                       const float* x, const uint8_t* y, int64_t n_rows, float* loss_sums,
+                       int32_t* correct, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Decision-tree plan: the classifier vad.py deploys
  * (learning/decision_classifier_trainer.py:26-35: sklearn
  * DecisionTreeClassifier, predict through sklearn_analyser.py:71) as a flat

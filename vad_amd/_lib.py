@@ -51,6 +51,11 @@ SIGNATURES = {
     "vad_features_ffn": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
     "vad_features_ffn_logits": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "vad_ffn_predict": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "vad_ffn_train_param_count": (c_i64, [c_i32, c_vp]),
+    "vad_ffn_train_steps": (c_int, [c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i64, c_vp,
+                                    c_vp, c_vp]),
+    "vad_ffn_train_eval_chunks": (c_i64, [c_i64]),
+    "vad_ffn_train_eval": (c_int, [c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "vad_tree_plan_create": (c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "vad_tree_plan_destroy": (c_int, [c_vp]),
     "vad_tree_predict": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),

@@ -806,6 +806,54 @@ int vad_ffn_predict(const vad_ffn_plan* ffn, const float* x, int64_t n, uint8_t*
   return (int)launch_ffn(ffn->net, 1, x, n, 0, 0, labels, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------
+// FFN training
+// ---------------------------------------------------------------------------
+static bool train_shape_ok(int32_t n_layers, const int32_t* dims) {
+  if (!dims || n_layers < 1 || n_layers > VAD_MAX_FFN_LAYERS) return false;
+  for (int l = 0; l <= n_layers; ++l)
+    if (dims[l] < 1 || dims[l] > 64) return false;
+  return dims[n_layers] <= 4;
+}
+
+int64_t vad_ffn_train_param_count(int32_t n_layers, const int32_t* dims) {
+  if (!train_shape_ok(n_layers, dims)) return -1;
+  int64_t c = 0;
+  for (int l = 0; l < n_layers; ++l) c += (int64_t)dims[l] * dims[l + 1] + dims[l + 1];
+  return c;
+}
+
+int vad_ffn_train_steps(int32_t n_layers, const int32_t* dims, float* state, int64_t n_models, const float* x,
+                        const uint8_t* y, int64_t n_rows, const int32_t* order, int64_t order_model_stride,
+                        int32_t batch, int64_t n_steps, const float* hyper, float* step_loss, void* stream) {
+  if (!train_shape_ok(n_layers, dims) || batch < 1 || batch > 64) return VAD_EINVAL;
+  if (n_models < 0 || n_models > INT32_MAX || n_rows < 0 || n_steps < 0 || order_model_stride < 0) return VAD_EINVAL;
+  if (n_steps > INT64_MAX / 64) return VAD_EINVAL;
+  if (order_model_stride != 0 && order_model_stride < n_steps * batch) return VAD_EINVAL;
+  if (n_models == 0 || n_steps == 0) return VAD_OK;
+  if (!state || !x || !y || !order || !hyper || n_rows == 0) return VAD_EINVAL;
+  if (ffn_train_lds_bytes(n_layers, dims, batch, true) > 160 * 1024) return VAD_EUNSUPPORTED;
+  return (int)launch_ffn_train(n_layers, dims, state, n_models, x, y, order, order_model_stride, batch, n_steps,
+                               hyper, step_loss, (hipStream_t)stream);
+}
+
+int64_t vad_ffn_train_eval_chunks(int64_t n_rows) {
+  if (n_rows < 0) return -1;
+  return n_rows / VAD_TRAIN_EVAL_CHUNK_ROWS + (n_rows % VAD_TRAIN_EVAL_CHUNK_ROWS != 0);
+}
+
+int vad_ffn_train_eval(int32_t n_layers, const int32_t* dims, const float* state, int64_t n_models, const float* x,
+                       const uint8_t* y, int64_t n_rows, float* loss_sums, int32_t* correct, void* stream) {
+  if (!train_shape_ok(n_layers, dims) || n_models < 0 || n_rows < 0) return VAD_EINVAL;
+  if (n_models == 0 || n_rows == 0) return VAD_OK;
+  if (!state || !x || !y || !loss_sums || !correct) return VAD_EINVAL;
+  const int64_t n_chunks = vad_ffn_train_eval_chunks(n_rows);
+  if (n_models > INT32_MAX / n_chunks) return VAD_EUNSUPPORTED;
+  if (ffn_train_lds_bytes(n_layers, dims, 64, false) > 160 * 1024) return VAD_EUNSUPPORTED;
+  return (int)launch_ffn_eval(n_layers, dims, state, n_models, x, y, n_rows, n_chunks, loss_sums, correct,
+                              (hipStream_t)stream);
+}
+
 size_t vad_mfcc_ffn_workspace_bytes(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, int64_t n_samples,
                                     int32_t frame_size, int32_t hop) {
   if (!plan || !ffn) return 0;

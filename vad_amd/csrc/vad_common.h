@@ -199,6 +199,16 @@ hipError_t launch_tree_rows(const TreeNode* nodes, int n_nodes, const float* x, 
 hipError_t launch_tree_windows(const TreeNode* nodes, const TreeNodeC* cnodes, int n_nodes,
                                const float* mfcc, int64_t n_rows,
                                int mfcc_n, int mode, uint8_t* labels, hipStream_t st);
+// FFN training (train_kernel.hip).  ffn_train_lds_bytes: LDS of one
+// workgroup of the step kernel (train) or of the evaluation kernel; the C
+// entries refuse what does not fit in 160 KiB before they launch.
+int64_t ffn_train_lds_bytes(int n_layers, const int32_t* dims, int batch, bool train);
+hipError_t launch_ffn_train(int n_layers, const int32_t* dims, float* state, int64_t n_models, const float* x,
+                            const uint8_t* y, const int32_t* order, int64_t order_stride, int batch, int64_t n_steps,
+                            const float* hyper, float* step_loss, hipStream_t st);
+hipError_t launch_ffn_eval(int n_layers, const int32_t* dims, const float* state, int64_t n_models, const float* x,
+                           const uint8_t* y, int64_t n_rows, int64_t n_chunks, float* loss_sums, int32_t* correct,
+                           hipStream_t st);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel and device
 // (`done`: one bit per device ordinal, a static of the launch site).

@@ -4,7 +4,8 @@ duck-typed ``predict`` protocol the analyser uses
 
 Weights are Keras-layout ``W (in, out)``, ``b (out,)`` float32, stored as an
 ``.npz`` with keys ``W0, b0, W1, b1, ...`` (the reference never committed
-trained weights).
+trained weights; ``vad_amd.train.FFNTrainer`` trains them on
+the device and saves this format).
 
 Arithmetic: the two specialised topologies (39-64-32-16-3, 13-64-64-N) run
 "split-f16" by default -- every GEMM operand split v = hi + lo into f16
