@@ -292,6 +292,74 @@ int vad_features_tree(const vad_tree_plan* tree, const float* mfcc, int64_t n_fr
                       int32_t mfcc_n, int32_t mode, uint8_t* labels, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Decision-tree training (learning/decision_classifier_trainer.py:26-30; the
+ * grid of learning/cross_validation.py:20-27): sklearn 1.7.2's Gini / best
+ * splitter over all features and unweighted rows, made deterministic (ties
+ * between features: the lowest feature, then the lowest position), for
+ * n_jobs jobs in one chain of launches.  DESIGN.md section 4 has the rule.
+ *
+ * x[i*n_features + f] (fp32, finite) and y[i] (class index < n_classes) are
+ * the device rows; order[f*n_rows + i] (int32, device) lists the rows by
+ * rising x[., f] (any order among equal values).  Job j trains on the rows r
+ * with mask[j*n_rows + r] != 0 (device; NULL: every job takes every row);
+ * jobs[j].n_rows must be their number.  Limits: 1 <= n_features <= 64,
+ * 2 <= n_classes <= 8, 1 <= n_rows < 2^27, 1 <= n_jobs <= 4096 (jobs of one
+ * row: at most 1024), all jobs' rows together < 2^31 - 4096.
+ *
+ * Job j's nodes are written at the sum of the earlier jobs' node_capacity, in
+ * level order (the root first, the two children of a node adjacent); a leaf
+ * has feature -1, threshold -2, left = right = -1.  feature / threshold /
+ * left / right / leaf / nan_left are what vad_tree_plan_create reads; value
+ * holds n_classes class counts per node.  status[j] is 0 or a sum of the
+ * VAD_TREE_TRAIN_* bits.  vad_tree_train_node_capacity(n_rows,
+ * min_samples_leaf) = 2*floor(n_rows / max(min_samples_leaf, 1)) - 1 (at least
+ * 1) always suffices; with less the job stops where its next level would not
+ * fit, nothing is written past its nodes, and the call returns VAD_ENOMEM.
+ *
+ * All arguments are checked before any HIP call.  The call returns after the
+ * stream has run it: it reads two integers back per level of the trees (the
+ * count is returned in *n_levels, may be NULL).  VAD_EINVAL after the launch:
+ * a job's mask does not hold jobs[j].n_rows rows, or a label >= n_classes.
+ * ------------------------------------------------------------------------- */
+#define VAD_TREE_TRAIN_MAX_CLASSES 8
+#define VAD_TREE_TRAIN_ROW_BITS 27
+#define VAD_TREE_TRAIN_OVERFLOW 1 /* status: node_capacity too small */
+#define VAD_TREE_TRAIN_BAD_ROWS 2 /* status: mask / n_rows / label mismatch */
+
+typedef struct vad_tree_job {
+  int64_t n_rows;
+  int64_t node_capacity;
+  int32_t max_depth;         /* >= 1 */
+  int32_t min_samples_split; /* >= 2 */
+  int32_t min_samples_leaf;  /* >= 1 */
+  int32_t reserved;          /* 0 */
+} vad_tree_job;
+
+typedef struct vad_tree_tables { /* device arrays; N = the sum of node_capacity */
+  int32_t* feature;              /* [N] */
+  double* threshold;             /* [N] */
+  int32_t* left;                 /* [N] */
+  int32_t* right;                /* [N] */
+  int32_t* leaf;                 /* [N] */
+  uint8_t* nan_left;             /* [N] */
+  int32_t* n_node_samples;       /* [N] */
+  int32_t* depth;                /* [N] */
+  int32_t* value;                /* [N * n_classes] */
+  int32_t* n_nodes;              /* [n_jobs] */
+  int32_t* status;               /* [n_jobs] */
+} vad_tree_tables;
+
+/* -1 for n_rows < 1 or min_samples_leaf < 1 */
+int64_t vad_tree_train_node_capacity(int64_t n_rows, int32_t min_samples_leaf);
+/* device bytes vad_tree_train needs for these jobs; 0 for arguments it refuses */
+size_t vad_tree_train_workspace_bytes(int64_t n_rows, int32_t n_features, int32_t n_classes, int32_t n_jobs,
+                                      const vad_tree_job* jobs);
+int vad_tree_train(const float* x, const uint8_t* y, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                   const int32_t* order, const uint8_t* mask, int32_t n_jobs, const vad_tree_job* jobs,
+                   const vad_tree_tables* tables, void* workspace, size_t workspace_bytes, int32_t* n_levels,
+                   void* stream);
+
+/* ---------------------------------------------------------------------------
  * Offline dataset export (dataset_creator.py:58-66 -> file_processing.py,
  * dataset/utils.py).
  * ------------------------------------------------------------------------- */

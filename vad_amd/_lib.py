@@ -60,6 +60,10 @@ SIGNATURES = {
     "vad_tree_plan_destroy": (c_int, [c_vp]),
     "vad_tree_predict": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "vad_features_tree": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "vad_tree_train_node_capacity": (c_i64, [c_i64, c_i32]),
+    "vad_tree_train_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32, c_i32, c_vp]),
+    "vad_tree_train": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp,
+                               c_vp]),
     "vad_simple_features": (c_int, [c_vp, c_i64, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp,
                                     c_vp]),
     "vad_scale_workspace_bytes": (c_sz, []),

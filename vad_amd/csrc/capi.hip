@@ -854,6 +854,61 @@ int vad_ffn_train_eval(int32_t n_layers, const int32_t* dims, const float* state
                               (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------
+// Decision-tree training
+// ---------------------------------------------------------------------------
+int64_t vad_tree_train_node_capacity(int64_t n_rows, int32_t min_samples_leaf) {
+  if (n_rows < 1 || min_samples_leaf < 1) return -1;
+  const int64_t c = 2 * (n_rows / min_samples_leaf) - 1;
+  return c < 1 ? 1 : c;
+}
+
+static bool tree_train_shape_ok(int64_t n_rows, int32_t n_features, int32_t n_classes, int32_t n_jobs,
+                                const vad_tree_job* jobs) {
+  if (n_rows < 1 || n_rows >= (1ll << VAD_TREE_TRAIN_ROW_BITS)) return false;
+  if (n_features < 1 || n_features > 64 || n_classes < 2 || n_classes > VAD_TREE_TRAIN_MAX_CLASSES) return false;
+  if (n_jobs < 1 || n_jobs > 4096 || !jobs) return false;
+  int64_t nodes = 0;
+  int single = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const vad_tree_job& b = jobs[j];
+    if (b.n_rows < 1 || b.n_rows > n_rows || b.max_depth < 1 || b.min_samples_split < 2 || b.min_samples_leaf < 1 ||
+        b.reserved != 0)
+      return false;
+    if (b.node_capacity < 1 || b.node_capacity > (1 << 28)) return false;
+    nodes += b.node_capacity;
+    single += b.n_rows == 1;
+  }
+  return nodes < (1ll << 31) && single <= 1024;
+}
+
+size_t vad_tree_train_workspace_bytes(int64_t n_rows, int32_t n_features, int32_t n_classes, int32_t n_jobs,
+                                      const vad_tree_job* jobs) {
+  if (!tree_train_shape_ok(n_rows, n_features, n_classes, n_jobs, jobs)) return 0;
+  return tree_train_ws_bytes(n_rows, n_features, n_jobs, jobs);
+}
+
+int vad_tree_train(const float* x, const uint8_t* y, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                   const int32_t* order, const uint8_t* mask, int32_t n_jobs, const vad_tree_job* jobs,
+                   const vad_tree_tables* tables, void* workspace, size_t workspace_bytes, int32_t* n_levels,
+                   void* stream) {
+  if (!tree_train_shape_ok(n_rows, n_features, n_classes, n_jobs, jobs)) return VAD_EINVAL;
+  if (!x || !y || !order || !tables || !workspace) return VAD_EINVAL;
+  const vad_tree_tables& t = *tables;
+  if (!t.feature || !t.threshold || !t.left || !t.right || !t.leaf || !t.nan_left || !t.n_node_samples || !t.depth ||
+      !t.value || !t.n_nodes || !t.status)
+    return VAD_EINVAL;
+  if (((uintptr_t)workspace & 255) || ((uintptr_t)t.threshold & 7)) return VAD_EINVAL;
+  if (!mask)
+    for (int j = 0; j < n_jobs; ++j)
+      if (jobs[j].n_rows != n_rows) return VAD_EINVAL;
+  const size_t need = tree_train_ws_bytes(n_rows, n_features, n_jobs, jobs);
+  if (need == 0) return VAD_EUNSUPPORTED;
+  if (workspace_bytes < need) return VAD_EINVAL;
+  return tree_train_run(x, y, n_rows, n_features, n_classes, order, mask, n_jobs, jobs, t, workspace, workspace_bytes,
+                        n_levels, (hipStream_t)stream);
+}
+
 size_t vad_mfcc_ffn_workspace_bytes(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, int64_t n_samples,
                                     int32_t frame_size, int32_t hop) {
   if (!plan || !ffn) return 0;

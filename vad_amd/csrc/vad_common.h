@@ -210,6 +210,13 @@ hipError_t launch_ffn_eval(int n_layers, const int32_t* dims, const float* state
                            const uint8_t* y, int64_t n_rows, int64_t n_chunks, float* loss_sums, int32_t* correct,
                            hipStream_t st);
 
+// Decision-tree training (tree_train_kernel.hip).  The C entries have checked
+// every argument; tree_train_ws_bytes is 0 where the sizes do not fit.
+size_t tree_train_ws_bytes(int64_t n, int F, int n_jobs, const vad_tree_job* jobs);
+int tree_train_run(const float* x, const uint8_t* y, int64_t n, int F, int K, const int32_t* order,
+                   const uint8_t* mask, int n_jobs, const vad_tree_job* jobs, const vad_tree_tables& out, void* ws,
+                   size_t ws_bytes, int32_t* n_levels, hipStream_t st);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel and device
 // (`done`: one bit per device ordinal, a static of the launch site).
 inline hipError_t ensure_dyn_lds(const void* fn, int bytes, std::atomic<unsigned long long>& done) {

@@ -23,6 +23,7 @@ from ._lib import check, lib, ptr, stream_ptr
 from .plan import _out
 
 _KEYS = ("feature", "threshold", "left", "right", "leaf", "nan_left", "classes")
+_TRAIN_KEYS = ("n_node_samples", "depth", "value")  # optional: written by a trained tree only
 
 
 class TreePlan:
@@ -61,7 +62,8 @@ class TreePlan:
 class TreeClassifier:
     """GPU decision tree with the sklearn ``predict`` protocol."""
 
-    def __init__(self, feature, threshold, left, right, leaf, nan_left, classes, n_features):
+    def __init__(self, feature, threshold, left, right, leaf, nan_left, classes, n_features,
+                 n_node_samples=None, depth=None, value=None):
         self.nan_left = np.asarray(nan_left, np.uint8)
         self.feature = np.asarray(feature, np.int32)
         self.threshold = np.asarray(threshold, np.float64)
@@ -70,6 +72,11 @@ class TreeClassifier:
         self.leaf = np.asarray(leaf, np.int32)
         self.classes_ = np.asarray(classes)
         self.n_features = int(n_features)
+        # what a trainer knows about its nodes (vad_amd.tree_train; None otherwise):
+        # rows, depth and class counts (n_nodes, n_classes) per node
+        self.n_node_samples = None if n_node_samples is None else np.asarray(n_node_samples, np.int32)
+        self.depth = None if depth is None else np.asarray(depth, np.int32)
+        self.value = None if value is None else np.asarray(value, np.int32)
         self._plan = None
 
     # -- construction ----------------------------------------------------
@@ -97,12 +104,14 @@ class TreeClassifier:
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
-            return cls(*(z[k] for k in _KEYS), int(z["n_features"]))
+            extra = {k: z[k] for k in _TRAIN_KEYS if k in z.files}
+            return cls(*(z[k] for k in _KEYS), int(z["n_features"]), **extra)
 
     def save(self, path):
         np.savez(path, feature=self.feature, threshold=self.threshold, left=self.left,
                  right=self.right, leaf=self.leaf, nan_left=self.nan_left, classes=self.classes_,
-                 n_features=np.int64(self.n_features))
+                 n_features=np.int64(self.n_features),
+                 **{k: getattr(self, k) for k in _TRAIN_KEYS if getattr(self, k) is not None})
 
     @property
     def plan(self) -> TreePlan:

@@ -1,0 +1,293 @@
+"""Training the decision tree on the device (the reference fits sklearn's
+``DecisionTreeClassifier(min_samples_split=22, max_depth=25,
+min_samples_leaf=20)`` in learning/decision_classifier_trainer.py:26-30 and
+chooses those parameters with a ``GridSearchCV`` over 7 x 4 x 4 settings in
+learning/cross_validation.py:20-27).
+
+    tree = TreeTrainer().fit(X, y)                    # a TreeClassifier
+    res = TreeTrainer().grid(X, y, [3, 5, 10, 15, 20, 25, 30], [2, 10, 22, 40],
+                             [1, 5, 20, 40], kfold(len(X), 3))
+
+The rule is sklearn 1.7.2's (Gini, best splitter, all features), with ties
+between features decided: the lowest feature, then the lowest position
+(DESIGN.md section 4).  ``fit_many`` grows any number of trees -- each a set
+of rows and its three parameters -- in one chain of launches
+(csrc/tree_train_kernel.hip); the rows are sorted once per call, by one
+``torch.sort``.  The kernels number a tree's nodes level by level; this
+module renumbers them to sklearn's preorder on the host.  The split chosen at
+a node depends on neither ``max_depth`` nor ``min_samples_split``, so the
+tree for smaller values of either is the big tree cut short: ``prune``.
+``grid`` therefore trains one tree per (fold, ``min_samples_leaf``) and prunes
+for the rest: the reference's 112 x 3 fits are 12 device jobs.
+
+There is no CPU path: the trees grow in the HIP kernels or the call raises.
+"""
+from __future__ import annotations
+
+import ctypes
+import time
+
+import numpy as np
+import torch
+
+from ._lib import VAD_ENOMEM, VadError, check, lib, stream_ptr
+from .tree import TreeClassifier
+
+MAX_FEATURES = 64
+MAX_CLASSES = 8
+MAX_ROWS = 1 << 27
+
+
+class _Job(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_int64), ("node_capacity", ctypes.c_int64), ("max_depth", ctypes.c_int32),
+                ("min_samples_split", ctypes.c_int32), ("min_samples_leaf", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+_TABLES = (("feature", torch.int32), ("threshold", torch.float64), ("left", torch.int32), ("right", torch.int32),
+           ("leaf", torch.int32), ("nan_left", torch.uint8), ("n_node_samples", torch.int32),
+           ("depth", torch.int32), ("value", torch.int32), ("n_nodes", torch.int32), ("status", torch.int32))
+
+
+class _Tables(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k, _ in _TABLES]
+
+
+def kfold(n, k):
+    """sklearn's unshuffled ``KFold(k)``: k consecutive blocks, the first
+    ``n % k`` one row longer; [(train_idx, test_idx), ...]."""
+    n, k = int(n), int(k)
+    if not 2 <= k <= n:
+        raise ValueError("kfold: need 2 <= k <= n")
+    sizes = np.full(k, n // k, np.int64)
+    sizes[:n % k] += 1
+    ends = np.cumsum(sizes)
+    idx = np.arange(n, dtype=np.int64)
+    return [(np.concatenate([idx[:e - s], idx[e:]]), idx[e - s:e]) for s, e in zip(sizes, ends)]
+
+
+def check_params(max_depth, min_samples_split, min_samples_leaf):
+    md, mss, msl = int(max_depth), int(min_samples_split), int(min_samples_leaf)
+    if md < 1 or mss < 2 or msl < 1 or max(md, mss, msl) >= 2 ** 31:
+        raise ValueError("need max_depth >= 1, min_samples_split >= 2, min_samples_leaf >= 1")
+    return md, mss, msl
+
+
+def check_rows(X, y):
+    """Shapes, limits and finiteness (ValueError), before anything touches the
+    device.  Returns X (float32, contiguous, as given: numpy or torch), the
+    class indices (uint8 numpy) and ``classes_``."""
+    if isinstance(X, torch.Tensor):
+        Xc = X.detach()
+        if Xc.dtype != torch.float32:
+            Xc = Xc.to(torch.float32)
+        Xc = Xc.contiguous()
+    else:
+        Xc = np.ascontiguousarray(X, np.float32)
+    if Xc.ndim != 2:
+        raise ValueError(f"X must be (n_rows, n_features), got {tuple(Xc.shape)}")
+    n, F = (int(v) for v in Xc.shape)
+    if not 1 <= F <= MAX_FEATURES:
+        raise ValueError(f"n_features must be 1..{MAX_FEATURES}, got {F}")
+    if not 1 <= n < MAX_ROWS:
+        raise ValueError(f"n_rows must be 1..2^27 - 1, got {n}")
+    yh = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
+    if yh.shape != (n,):
+        raise ValueError(f"y must be ({n},), got {yh.shape}")
+    finite = bool(torch.isfinite(Xc).all()) if isinstance(Xc, torch.Tensor) else bool(np.isfinite(Xc).all())
+    if not finite:
+        raise ValueError("X holds NaN or infinity: training rows must be finite")
+    classes, idx = np.unique(yh, return_inverse=True)
+    if len(classes) > MAX_CLASSES:
+        raise ValueError(f"{len(classes)} classes, at most {MAX_CLASSES}")
+    return Xc, idx.astype(np.uint8).reshape(n), classes
+
+
+def preorder(t):
+    """A level-ordered node table (dict of arrays with ``depth``) renumbered
+    node, left subtree, right subtree -- sklearn's depth-first numbering."""
+    left, right, depth = t["left"], t["right"], t["depth"]
+    m = len(left)
+    size = np.ones(m, np.int64)
+    inner = left >= 0
+    top = int(depth.max()) if m else 0
+    for d in range(top - 1, -1, -1):
+        i = np.flatnonzero(inner & (depth == d))
+        size[i] = 1 + size[left[i]] + size[right[i]]
+    new = np.zeros(m, np.int64)
+    for d in range(top):
+        i = np.flatnonzero(inner & (depth == d))
+        new[left[i]] = new[i] + 1
+        new[right[i]] = new[i] + 1 + size[left[i]]
+    out = {}
+    for k, v in t.items():
+        a = np.empty_like(v)
+        a[new] = v
+        out[k] = a
+    for k in ("left", "right"):
+        a = out[k]
+        a[a >= 0] = new[a[a >= 0]].astype(a.dtype)
+    return out
+
+
+_NODE_KEYS = ("feature", "threshold", "left", "right", "leaf", "nan_left", "n_node_samples", "depth", "value")
+
+
+def _table(tree):
+    if tree.n_node_samples is None or tree.depth is None or tree.value is None:
+        raise ValueError("the tree carries no n_node_samples / depth / value: it was not trained here")
+    return {k: getattr(tree, k) for k in _NODE_KEYS}
+
+
+def prune_table(t, max_depth, min_samples_split):
+    """The preorder table ``t`` cut where ``depth >= max_depth`` or
+    ``n_node_samples < min_samples_split``, renumbered in preorder."""
+    depth, left, right = t["depth"], t["left"], t["right"]
+    cut = (depth >= int(max_depth)) | (t["n_node_samples"] < int(min_samples_split))
+    inner = (left >= 0) & ~cut
+    keep = np.zeros(len(left), bool)
+    keep[0] = True
+    for d in range(int(depth.max())):
+        i = np.flatnonzero(keep & inner & (depth == d))
+        keep[left[i]] = True
+        keep[right[i]] = True
+    new = np.cumsum(keep) - 1  # dropping whole subtrees keeps the preorder
+    out = {k: np.array(v[keep]) for k, v in t.items()}
+    leafed = ~inner[keep]
+    out["feature"][leafed] = -1
+    out["threshold"][leafed] = -2.0
+    out["nan_left"][leafed] = 0
+    for k in ("left", "right"):
+        a = out[k]
+        a[leafed] = -1
+        a[~leafed] = new[a[~leafed]].astype(a.dtype)
+    return out
+
+
+def prune(tree, max_depth, min_samples_split):
+    """The tree that training with a smaller ``max_depth`` and / or a larger
+    ``min_samples_split`` (same rows, same ``min_samples_leaf``) gives."""
+    t = prune_table(_table(tree), max_depth, min_samples_split)
+    return TreeClassifier(*(t[k] for k in _NODE_KEYS[:6]), tree.classes_, tree.n_features,
+                          n_node_samples=t["n_node_samples"], depth=t["depth"], value=t["value"])
+
+
+class TreeTrainer:
+    """Exact Gini trees on the device, the reference's parameters as defaults."""
+
+    def __init__(self, max_depth=25, min_samples_split=22, min_samples_leaf=20):
+        self.max_depth, self.min_samples_split, self.min_samples_leaf = check_params(max_depth, min_samples_split,
+                                                                                     min_samples_leaf)
+        self.last_levels = None  # levels the last call ran (its deepest tree + 1)
+        self.last_call_seconds = None  # host clock around the last vad_tree_train (it returns when the stream has run it)
+
+    def fit(self, X, y):
+        return self.fit_many(X, y, [(None, self.max_depth, self.min_samples_split, self.min_samples_leaf)])[0]
+
+    def fit_many(self, X, y, jobs, node_capacity=None):
+        """One tree per job ``(rows, max_depth, min_samples_split,
+        min_samples_leaf)``; ``rows``: indices into X without repeats, in any
+        order, or None for all.  ``node_capacity`` (tests): nodes to provide
+        per job instead of the bound that always suffices."""
+        Xc, yi, classes = check_rows(X, y)
+        n, F = (int(v) for v in Xc.shape)
+        K = max(2, len(classes))
+        if not jobs:
+            return []
+        params, row_sets = [], []
+        for rows, md, mss, msl in jobs:
+            params.append(check_params(md, mss, msl))
+            if rows is not None:
+                rows = np.asarray(rows.cpu() if isinstance(rows, torch.Tensor) else rows).astype(np.int64).ravel()
+                if rows.size < 1 or rows.min() < 0 or rows.max() >= n or np.unique(rows).size != rows.size:
+                    raise ValueError("a job's rows must be distinct indices into X, at least one")
+            row_sets.append(rows)
+        if not torch.cuda.is_available():
+            raise RuntimeError("TreeTrainer needs the GPU: there is no CPU path")
+        dev = Xc.device if isinstance(Xc, torch.Tensor) and Xc.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        with torch.cuda.device(dev):
+            Xd = Xc if isinstance(Xc, torch.Tensor) and Xc.is_cuda else torch.as_tensor(Xc).to(dev)
+            yd = torch.from_numpy(yi).to(dev)
+            order = torch.sort(Xd.t().contiguous(), dim=1, stable=True).indices.to(torch.int32).contiguous()
+            J = len(jobs)
+            mask = None
+            if any(r is not None for r in row_sets):
+                mask = torch.zeros((J, n), dtype=torch.uint8, device=dev)
+                for j, r in enumerate(row_sets):
+                    if r is None:
+                        mask[j] = 1
+                    else:
+                        mask[j, torch.from_numpy(r).to(dev)] = 1
+            desc = (_Job * J)()
+            for j, ((md, mss, msl), r) in enumerate(zip(params, row_sets)):
+                nr = n if r is None else int(r.size)
+                cap = int(lib().vad_tree_train_node_capacity(nr, msl)) if node_capacity is None else int(node_capacity)
+                desc[j] = _Job(nr, cap, md, mss, msl, 0)
+            total = sum(int(d.node_capacity) for d in desc)
+            need = int(lib().vad_tree_train_workspace_bytes(n, F, K, J, desc))
+            if need == 0:
+                raise ValueError("vad_tree_train refuses these sizes (include/vad_amd.h lists the limits)")
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            out = {k: torch.empty(J if k in ("n_nodes", "status") else total * (K if k == "value" else 1), dtype=dt,
+                                  device=dev) for k, dt in _TABLES}
+            tb = _Tables(*(out[k].data_ptr() for k, _ in _TABLES))
+            levels = ctypes.c_int32(0)
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            rc = lib().vad_tree_train(Xd.data_ptr(), yd.data_ptr(), n, F, K, order.data_ptr(),
+                                      None if mask is None else mask.data_ptr(), J, desc, ctypes.byref(tb),
+                                      ws.data_ptr(), need, ctypes.byref(levels), stream_ptr())
+            self.last_call_seconds = time.perf_counter() - t0
+            if rc == VAD_ENOMEM:
+                status = out["status"].cpu().numpy()
+                raise VadError(f"vad_tree_train: node storage too small for jobs {np.flatnonzero(status & 1).tolist()}")
+            check(rc, "vad_tree_train")
+            self.last_levels = int(levels.value)
+            host = {k: v.cpu().numpy() for k, v in out.items()}
+        host["value"] = host["value"].reshape(total, K)
+        trees, at = [], 0
+        for j in range(J):
+            m = int(host["n_nodes"][j])
+            t = preorder({k: host[k][at:at + m] for k in _NODE_KEYS})
+            at += int(desc[j].node_capacity)
+            trees.append(TreeClassifier(*(t[k] for k in _NODE_KEYS[:6]), classes, F, n_node_samples=t["n_node_samples"],
+                                        depth=t["depth"], value=t["value"][:, :max(len(classes), 1)]))
+        return trees
+
+    def grid(self, X, y, max_depth, min_samples_split, min_samples_leaf, folds):
+        """Cross-validated accuracy of every (max_depth, min_samples_split,
+        min_samples_leaf) over the caller's ``folds`` [(train_idx, test_idx),
+        ...] (``kfold`` gives sklearn's).  One device job per (fold,
+        min_samples_leaf), at the largest depth and the smallest
+        min_samples_split; the other settings are pruned from it.  Returns a
+        dict: "params" (list of dicts, in sklearn's ParameterGrid order),
+        "mean_test_score", "best_index_", "best_params_", "best_score_" (the
+        first maximum, as GridSearchCV ranks)."""
+        mds = [int(v) for v in np.atleast_1d(max_depth)]
+        msss = [int(v) for v in np.atleast_1d(min_samples_split)]
+        msls = [int(v) for v in np.atleast_1d(min_samples_leaf)]
+        folds = [(np.asarray(a, np.int64), np.asarray(b, np.int64)) for a, b in folds]
+        if not (mds and msss and msls and folds):
+            raise ValueError("grid needs at least one value per parameter and one fold")
+        Xc, yi, classes = check_rows(X, y)
+        jobs = [(tr, max(mds), min(msss), msl) for tr, _ in folds for msl in msls]
+        big = self.fit_many(Xc, yi, jobs)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        Xd = Xc if isinstance(Xc, torch.Tensor) and Xc.is_cuda else torch.as_tensor(Xc).to(dev)
+        yd = torch.from_numpy(yi).to(Xd.device)
+        # fit_many saw class indices: its classes_ are the indices present
+        params = [dict(max_depth=md, min_samples_leaf=msl, min_samples_split=mss)
+                  for md in mds for msl in msls for mss in msss]
+        score = np.zeros((len(params), len(folds)))
+        for fi, (_, test) in enumerate(folds):
+            ti = torch.from_numpy(test).to(Xd.device)
+            xt, yt = Xd[ti].contiguous(), yd[ti]
+            for pi, p in enumerate(params):
+                tree = prune(big[fi * len(msls) + msls.index(p["min_samples_leaf"])], p["max_depth"],
+                             p["min_samples_split"])
+                got = torch.from_numpy(tree.classes_.astype(np.uint8)).to(Xd.device)[tree.predict_device(xt).long()]
+                score[pi, fi] = float((got == yt).double().mean())
+        mean = score.mean(axis=1)
+        best = int(np.argmax(mean))
+        return {"params": params, "mean_test_score": mean, "split_test_score": score, "best_index_": best,
+                "best_params_": params[best], "best_score_": float(mean[best])}
