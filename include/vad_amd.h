@@ -461,6 +461,40 @@ int vad_stream_hops_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, floa
 int vad_stream_step(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, const float* frames,
                     int64_t frame_stride, int32_t frame_len, int64_t n_streams, float* ring,
                     int32_t* count, uint8_t* labels, float* mfcc_scratch, void* stream);
+/* The streaming entries with the decision tree (the classifier vad.py
+ * deploys) in place of the FFN: vad_stream_hops_tree(_i16) is
+ * vad_stream_hops(_i16) -- one wave per stream, n_hops hops per launch, the
+ * same front end bit for bit -- ending in a walk of the tree that is uniform
+ * over the wave; vad_stream_step_tree is vad_stream_step (the clip MFCC
+ * kernel, then the ring step), the only streaming form for a windowed or
+ * generic-fft_n plan.  labels are class indices (vad_tree_predict), 255
+ * while a stream has seen fewer than five frames.
+ * walk: VAD_TREE_WALK_AUTO walks the compact node table from LDS when it fits
+ * (n_nodes <= vad_stream_tree_max_lds_nodes(plan): the plan's hop tables, the
+ * 16-B nodes and one wave's scratch within 160 KiB) and from global memory
+ * otherwise; VAD_TREE_WALK_GLOBAL always walks from global memory.  Both give
+ * the same labels.
+ * Refusals: those of vad_stream_hops, checked before any device call
+ * (VAD_EINVAL for null plans, bad sizes, strides and layouts; after the
+ * n_streams == 0 / n_hops == 0 return, VAD_EINVAL for a null buffer and
+ * VAD_EUNSUPPORTED for a generic or windowed plan), plus VAD_EINVAL for any
+ * other `walk` and for a tree with n_features > 3 * mfcc_n (as
+ * vad_features_tree: a node's feature must lie in the window's row). */
+#define VAD_TREE_WALK_AUTO 0
+#define VAD_TREE_WALK_GLOBAL 1
+int vad_stream_hops_tree(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames, int64_t frame_stride,
+                         int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len, int64_t n_streams,
+                         int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels,
+                         int64_t label_block_stride, int32_t walk, void* stream);
+int vad_stream_hops_tree_i16(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                             int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                             int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride, float* ring,
+                             int32_t* count, uint8_t* labels, int64_t label_block_stride, int32_t walk, void* stream);
+int vad_stream_step_tree(const vad_mfcc_plan* plan, const vad_tree_plan* tree, const float* frames,
+                         int64_t frame_stride, int32_t frame_len, int64_t n_streams, float* ring, int32_t* count,
+                         uint8_t* labels, float* mfcc_scratch, void* stream);
+/* largest table the hop kernel walks from LDS; -1 on a bad plan */
+int64_t vad_stream_tree_max_lds_nodes(const vad_mfcc_plan* plan);
 /* Replay a captured hipGraph (hipGraphExec_t) on `stream`: the per-hop step
  * of a StreamBatch captured with its host I/O (the H2D copy of every
  * stream's new samples from pinned memory, the hop kernel, the D2H copy of

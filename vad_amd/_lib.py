@@ -24,6 +24,8 @@ FEAT_ANALYSER = 0
 FEAT_OFFLINE = 1
 FFN_EXACT_F32 = 0
 FFN_SPLIT_F16 = 1
+TREE_WALK_AUTO = 0
+TREE_WALK_GLOBAL = 1
 
 c_i32, c_i64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
 c_int = ctypes.c_int
@@ -88,6 +90,13 @@ SIGNATURES = {
                                     c_vp, c_vp, c_i64, c_vp]),
     "vad_stream_step": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp,
                                 c_vp]),
+    "vad_stream_hops_tree": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32, c_i64, c_vp,
+                                     c_vp, c_vp, c_i64, c_i32, c_vp]),
+    "vad_stream_hops_tree_i16": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32, c_i64,
+                                         c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
+    "vad_stream_step_tree": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp]),
+    "vad_stream_tree_max_lds_nodes": (c_i64, [c_vp]),
     "vad_graph_launch": (c_int, [c_vp, c_vp]),
     "vad_graph_plan_create": (c_int, [c_vp, c_vp, c_vp]),
     "vad_graph_plan_launch": (c_int, [c_vp, c_vp]),

@@ -1075,6 +1075,72 @@ int vad_stream_step(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, const fl
                                 labels, st);
 }
 
+// The same entries with the decision tree (stream_tree_kernel.hip): the
+// checks of stream_hops_entry in its order, the tree's feature count in place
+// of the network's input width (a node's feature index is an offset into the
+// wave's LDS row), and the walk selector.
+int64_t vad_stream_tree_max_lds_nodes(const vad_mfcc_plan* plan) {
+  if (!plan || !plan->hop_blob || plan->hop_blob_n <= 0) return -1;
+  return stream_tree_max_lds_nodes(plan->hop_blob_n);
+}
+
+static int stream_hops_tree_entry(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                                  int64_t frame_stride, int32_t frame_len, const void* hop, int hop_bytes,
+                                  int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,
+                                  int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels,
+                                  int64_t label_block_stride, int32_t walk, void* stream) {
+  if (!plan || !tree || n_streams < 0 || n_hops < 0 || frame_len <= 0 || frame_len > 1024 || hop_len <= 0 ||
+      hop_len > frame_len || frame_stride < frame_len || hop_stride < hop_len)
+    return VAD_EINVAL;
+  if (walk != VAD_TREE_WALK_AUTO && walk != VAD_TREE_WALK_GLOBAL) return VAD_EINVAL;
+  if (n_hops > 1 && label_block_stride < n_streams) return VAD_EINVAL;  // label rows of two hops would overlap
+  if (n_hops > 1 && !vad_hop_layout_disjoint(n_streams, n_hops, hop_block_stride, hop_stride, hop_len))
+    return VAD_EINVAL;
+  if (n_streams == 0 || n_hops == 0) return VAD_OK;
+  if (!frames || !hop || !ring || !count || !labels) return VAD_EINVAL;
+  if (tree->n_features > 3 * plan->host.mfcc_n) return VAD_EINVAL;
+  if (plan->generic()) return VAD_EUNSUPPORTED;  // its FFT is the 256-point Stockham of fft_n = 512
+  if (plan->spec == kSpecWindow) return VAD_EUNSUPPORTED;  // its table blob carries no analysis window
+  return (int)launch_stream_hop_tree(plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps,
+                                     tree->cnodes_dev, tree->nodes_dev, tree->n_nodes, walk == VAD_TREE_WALK_GLOBAL,
+                                     frames, frame_stride, frame_len, hop, hop_bytes, hop_stride, hop_len, n_streams,
+                                     plan->host.mfcc_n, ring, count, labels, n_hops, hop_block_stride,
+                                     label_block_stride, (hipStream_t)stream);
+}
+
+int vad_stream_hops_tree(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames, int64_t frame_stride,
+                         int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len, int64_t n_streams,
+                         int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels,
+                         int64_t label_block_stride, int32_t walk, void* stream) {
+  return stream_hops_tree_entry(plan, tree, frames, frame_stride, frame_len, hop, 4, hop_stride, hop_len, n_streams,
+                                n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk, stream);
+}
+
+int vad_stream_hops_tree_i16(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                             int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                             int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride, float* ring,
+                             int32_t* count, uint8_t* labels, int64_t label_block_stride, int32_t walk, void* stream) {
+  return stream_hops_tree_entry(plan, tree, frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len, n_streams,
+                                n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk, stream);
+}
+
+int vad_stream_step_tree(const vad_mfcc_plan* plan, const vad_tree_plan* tree, const float* frames,
+                         int64_t frame_stride, int32_t frame_len, int64_t n_streams, float* ring, int32_t* count,
+                         uint8_t* labels, float* mfcc_scratch, void* stream) {
+  if (!plan || !tree || n_streams < 0 || frame_len <= 0 || frame_stride < 0) return VAD_EINVAL;
+  if (n_streams == 0) return VAD_OK;
+  if (!frames || !ring || !count || !labels || !mfcc_scratch) return VAD_EINVAL;
+  if (tree->n_features > 3 * plan->host.mfcc_n) return VAD_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (plan->generic())
+    VAD_TRY(launch_generic(0, plan->dev, frames, frame_stride, frame_len, n_streams, plan->fft_n, plan->tw_gen,
+                           mfcc_scratch, st));
+  else
+    VAD_TRY(launch_mfcc(0, plan->dev, launch_spec(plan), frames, frame_stride, frame_len, n_streams, mfcc_scratch, st));
+  return (int)launch_stream_tree_ring(tree->cnodes_dev, tree->n_nodes, mfcc_scratch, ring, count, n_streams,
+                                      plan->host.mfcc_n, labels, st);
+}
+
 // ---------------------------------------------------------------------------
 // Streaming segments (stream_segments_kernel.hip)
 // ---------------------------------------------------------------------------

@@ -22,26 +22,12 @@
 // of a 24-B node; larger tables are walked from global memory.
 #include "vad_common.h"
 #include "features.h"
+#include "tree_walk.h"
 
 namespace vad {
 
 constexpr int kTreeWin = 256;                   // windows per block
 constexpr int kTreeXStride = 3 * kMaxCoefs + 1;  // floats per LDS feature row (49: odd)
-
-__device__ __forceinline__ int tree_walk(const TreeNode* __restrict__ nodes, int n_nodes,
-                                         const float* __restrict__ x, int x_step) {
-  int node = 0;
-  // every root-to-leaf path has < n_nodes edges; the bound only guards a
-  // malformed table against looping forever
-  for (int it = 0; it < n_nodes; ++it) {
-    const TreeNode nd = nodes[node];
-    if (nd.feature < 0) return nd.leaf;
-    const float xv = x[nd.feature * x_step];
-    const bool left = xv != xv ? nd.nan_left != 0 : (double)xv <= nd.threshold;
-    node = left ? nd.left : nd.right;
-  }
-  return 0;
-}
 
 // Feature rows x[i*dim + f] (vad_tree_predict).
 __global__ __launch_bounds__(256) void tree_rows_kernel(const TreeNode* __restrict__ nodes,
@@ -55,18 +41,6 @@ __global__ __launch_bounds__(256) void tree_rows_kernel(const TreeNode* __restri
 
 // Windows of an MFCC sequence (vad_features_tree), 256 per block iteration.
 constexpr int kLdsNodes = 3072;  // 48 KB of compact nodes
-
-__device__ __forceinline__ int tree_walk_c(const TreeNodeC* nodes, int n_nodes, const float* x) {
-  int node = 0;
-  for (int it = 0; it < n_nodes; ++it) {
-    const TreeNodeC nd = nodes[node];
-    if (nd.feature < 0) return -1 - nd.feature;
-    const float xv = x[nd.feature & 0xffff];
-    const bool left = xv != xv ? (nd.feature >> 30) != 0 : xv <= nd.thr;
-    node = left ? nd.left : nd.right;
-  }
-  return 0;
-}
 
 template <int MN, bool LDSN>
 __global__ __launch_bounds__(256) void tree_window_kernel(const TreeNode* __restrict__ nodes,

@@ -152,6 +152,18 @@ hipError_t launch_stream_hop(const MfccDev* plan, const float* blob, int blob_n,
                              int64_t hop_kstride, int64_t lab_kstride, hipStream_t st);
 hipError_t launch_stream_push(float* frames, int64_t fstride, int len, const void* hop, int hop_bytes,
                               int64_t hstride, int hlen, int64_t n_streams, hipStream_t st);
+// The hop kernel and the ring step with the decision tree
+// (stream_tree_kernel.hip).  stream_tree_max_lds_nodes: the largest table the
+// hop kernel walks from LDS beside a blob of blob_n floats; force_global walks
+// a smaller one from global memory too.
+int64_t stream_tree_max_lds_nodes(int blob_n);
+hipError_t launch_stream_hop_tree(const float* blob, int blob_n, int nf, int n_taps, const TreeNodeC* cnodes,
+                                  const TreeNode* nodes, int n_nodes, bool force_global, float* frames,
+                                  int64_t fstride, int len, const void* hop, int hop_bytes, int64_t hstride, int hlen,
+                                  int64_t n_streams, int mfcc_n, float* ring, int* count, uint8_t* labels, int n_hops,
+                                  int64_t hop_kstride, int64_t lab_kstride, hipStream_t st);
+hipError_t launch_stream_tree_ring(const TreeNodeC* cnodes, int n_nodes, const float* newrow, float* ring, int* count,
+                                   int64_t n_streams, int mfcc_n, uint8_t* labels, hipStream_t st);
 hipError_t launch_preemphasis(const float* x, float* y, int64_t n_rows, int64_t row_len, int64_t stride, float a,
                               hipStream_t st);
 // Streaming segments (stream_segments_kernel.hip): n_hops hops of every

@@ -15,6 +15,11 @@ labels[s] after a step is the class of stream s's window centred three steps
 earlier, or 255 during each stream's first five steps (feed_frame returns
 None for its first five calls, :48-50).
 
+The classifier is an FFN or the decision tree vad.py deploys (vad.py:17,52):
+with a TreeClassifier both forms end in a walk of the tree instead
+(vad_stream_hops_tree: the node table staged in LDS, one wave-uniform path
+per stream and hop; vad_stream_step_tree), and labels are class indices.
+
 Host I/O (C5's end-to-end rate includes the copies):
 attach_host_io() adds pinned host buffers ``host_inputs`` (K, S, hop) and
 ``host_labels`` (K, S); step_host() runs one step from the first to the
@@ -60,6 +65,9 @@ from . import _lib
 from .config import MfccConfig
 from .ffn import FFNClassifier
 from .plan import MfccPlan
+from .tree import TreeClassifier
+
+_TREE_WALKS = {"auto": _lib.TREE_WALK_AUTO, "global": _lib.TREE_WALK_GLOBAL}
 
 
 def hop_rows_disjoint(n_streams, n_hops, block_stride, hop_stride, hop_len):
@@ -76,13 +84,35 @@ def hop_rows_disjoint(n_streams, n_hops, block_stride, hop_stride, hop_len):
 
 
 class StreamBatch:
+    """S analyser streams with one classifier: an FFNClassifier (or its
+    layers), or a decision tree -- a TreeClassifier, or a fitted sklearn
+    DecisionTreeClassifier converted by TreeClassifier.from_sklearn, as
+    VadPipeline takes them.  ``ffn`` and ``classifier`` both hold it.
+
+    With a tree every form of a step is the FFN batch's (step, step_block in
+    either layout, int16 input, kernel="three", capture, step_host,
+    host_pipeline, segmenter); the hop kernel is vad_stream_hops_tree, the
+    three-kernel form ends in vad_stream_step_tree.  ``label_block`` holds
+    class *indices* (uint8) as TreeClassifier.window_labels gives them, 255
+    during a stream's first five hops: ``classes_[index]`` is the value
+    sklearn's predict returns, and segmenter(active=...) takes the index.
+    tree_walk="auto" walks the node table from LDS when it fits
+    (vad_stream_tree_max_lds_nodes) and from global memory otherwise;
+    "global" always walks from global memory (same labels)."""
 
     def __init__(self, n_streams, ffn, cfg: MfccConfig = MfccConfig(), device=None, kernel="hop",
-                 hops_per_step=1, input_dtype=torch.float32):
+                 hops_per_step=1, input_dtype=torch.float32, tree_walk="auto"):
         if input_dtype not in (torch.float32, torch.int16):
             raise ValueError("input_dtype must be torch.float32 or torch.int16")
-        if not isinstance(ffn, FFNClassifier):
-            ffn = FFNClassifier(ffn)
+        if tree_walk not in _TREE_WALKS:
+            raise ValueError("tree_walk must be 'auto' or 'global'")
+        if not isinstance(ffn, (FFNClassifier, TreeClassifier)):
+            ffn = TreeClassifier.from_sklearn(ffn) if TreeClassifier.looks_like_sklearn_tree(ffn) \
+                else FFNClassifier(ffn)
+        self.is_tree = isinstance(ffn, TreeClassifier)
+        self.tree_walk = tree_walk
+        if self.is_tree and ffn.n_features > 3 * cfg.n_mfcc:
+            raise ValueError(f"the tree reads {ffn.n_features} features; a window has 3 * n_mfcc = {3 * cfg.n_mfcc}")
         if cfg.preemph is not None:
             raise ValueError("pre-emphasis is a clip-level stage (VadPipeline); streams take raw frames")
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
@@ -91,6 +121,7 @@ class StreamBatch:
         if kernel == "hop" and cfg.window is not None:
             raise ValueError("the one-kernel hop has no analysis window; use kernel='three'")
         self.cfg, self.ffn, self.n, self.kernel = cfg, ffn, int(n_streams), kernel
+        self.classifier = ffn
         self.plan = MfccPlan.from_config(cfg)
         S, L, H, C = self.n, cfg.frame_size, cfg.hop, cfg.n_mfcc
         if not 0 < H <= L:
@@ -136,10 +167,12 @@ class StreamBatch:
         the current stream."""
         if getattr(self, "_hop_head", None) is None:
             L = self.cfg.frame_size
-            self._hop_fn = _lib.lib().vad_stream_hops_i16 if self._i16 else _lib.lib().vad_stream_hops
-            self._hop_name = "vad_stream_hops_i16" if self._i16 else "vad_stream_hops"
+            self._hop_name = ("vad_stream_hops_tree" if self.is_tree else "vad_stream_hops") + \
+                ("_i16" if self._i16 else "")
+            self._hop_fn = getattr(_lib.lib(), self._hop_name)
             self._hop_head = (self.plan.handle, self.ffn.plan.handle, _lib.ptr(self.frames), L, L)
             self._hop_mid = (_lib.ptr(self.ring), _lib.ptr(self.count))
+            self._hop_walk = (_TREE_WALKS[self.tree_walk],) if self.is_tree else ()
             self._hop_labels = {}
         lab = self.labels if labels is None else labels
         key = (lab.data_ptr(), n_hops)
@@ -148,7 +181,7 @@ class StreamBatch:
             tail = (ctypes.c_void_p(lab.data_ptr()), lab.stride(0) if lab.dim() == 2 else 0)
             self._hop_labels[key] = tail
         rc = self._hop_fn(*self._hop_head, ctypes.c_void_p(h.data_ptr()), h.stride(-2), self.cfg.hop, self.n,
-                          n_hops, h.stride(0) if h.dim() == 3 else 0, *self._hop_mid, *tail,
+                          n_hops, h.stride(0) if h.dim() == 3 else 0, *self._hop_mid, *tail, *self._hop_walk,
                           _lib.stream_ptr() if stream is None else stream)
         if rc:
             _lib.check(rc, self._hop_name)
@@ -160,10 +193,11 @@ class StreamBatch:
         push = lib.vad_stream_push_hop_i16 if self._i16 else lib.vad_stream_push_hop
         _lib.check(push(_lib.ptr(self.frames), L, L, ctypes.c_void_p(h.data_ptr()), h.stride(0), H, self.n, st),
                    "vad_stream_push_hop_i16" if self._i16 else "vad_stream_push_hop")
-        _lib.check(lib.vad_stream_step(
+        step = lib.vad_stream_step_tree if self.is_tree else lib.vad_stream_step
+        _lib.check(step(
             self.plan.handle, self.ffn.plan.handle, _lib.ptr(self.frames), L, L, self.n,
             _lib.ptr(self.ring), _lib.ptr(self.count), ctypes.c_void_p(labels.data_ptr()),
-            _lib.ptr(self.scratch), st), "vad_stream_step")
+            _lib.ptr(self.scratch), st), "vad_stream_step_tree" if self.is_tree else "vad_stream_step")
 
     def _body(self, hop=None):
         """One hop (K = 1) from `hop` or the static input."""
