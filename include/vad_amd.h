@@ -382,6 +382,61 @@ int64_t vad_format_csv_rows(const float* rows, int64_t n_rows, int32_t n_cols, d
                             char* buf, int64_t buf_size);
 
 /* ---------------------------------------------------------------------------
+ * Dataset CSV import: the text that write_features / vad_format_csv_rows
+ * wrote, back into feature rows and labels on the device (load_csv,
+ * file_processing.py:151-184; create_file_index, file_index.py:7-23).
+ *
+ * `bytes` is the text on the device.  Lines end in "\r\n" or "\n"; the last
+ * line may lack its terminator; a final '\n' starts no line.  The three
+ * calls run in this order on one stream:
+ *
+ *   vad_csv_count_lines  writes the number of lines to *n_lines (device) and
+ *                        leaves the per-tile carries in `ws`;
+ *   vad_csv_index        from those carries (same bytes, n_bytes and ws):
+ *                        index[r - skip] = base + byte offset of line r for
+ *                        skip <= r < skip + capacity -- create_file_index's
+ *                        offsets when base is the text's offset in its file;
+ *   vad_csv_parse        rows of n_cols comma-separated fields, one per index
+ *                        entry (row r ends where row r + 1 starts, the last
+ *                        at n_bytes).  X[r][j] = field columns[j] (host array
+ *                        of n_used <= VAD_CSV_MAX_USED indices; NULL: columns
+ *                        0 .. n_cols-2, n_used = n_cols - 1), the correctly
+ *                        rounded double of the text cast once to float32, or
+ *                        the double itself (out_f64 != 0); y[r] =
+ *                        int(float(last field)).
+ *
+ * row_status[r] is 0 or a sum of VAD_CSV_ROW_*.  HOST: a used field that the
+ * device does not decide (more than 19 significant digits, an unresolved
+ * rounding, blanks, a signed nan, anything outside
+ * [+-]?(d+[.d*]|.d+)([eE][+-]?d+)?, nan, [+-]?inf, [+-]?infinity); the caller
+ * parses that row itself.  MALFORMED: not n_cols fields, more than
+ * VAD_CSV_MAX_LINE bytes, or offsets outside the text.  LABEL: a label
+ * outside 0..255.  X and y of a row with a nonzero status are unspecified.
+ *
+ * The scans run on tiles of VAD_CSV_TILE bytes, VAD_CSV_CARRY_PASS tile
+ * counts per pass of the one carry workgroup.  VAD_EINVAL: a null pointer,
+ * a negative size, skip or capacity, n_cols < 2 or > VAD_CSV_MAX_COLS, n_used
+ * outside 1..VAD_CSV_MAX_USED, a column outside 0..n_cols-1, a misaligned
+ * output, a workspace below vad_csv_workspace_bytes(n_bytes).
+ * ------------------------------------------------------------------------- */
+#define VAD_CSV_TILE 4096
+#define VAD_CSV_CARRY_PASS 256
+#define VAD_CSV_MAX_LINE 4096
+#define VAD_CSV_MAX_COLS 2048
+#define VAD_CSV_MAX_USED 1024
+#define VAD_CSV_ROW_HOST 1
+#define VAD_CSV_ROW_MALFORMED 2
+#define VAD_CSV_ROW_LABEL 4
+size_t vad_csv_workspace_bytes(int64_t n_bytes); /* 0 for n_bytes < 0 */
+int vad_csv_count_lines(const uint8_t* bytes, int64_t n_bytes, int64_t* n_lines, void* ws, size_t ws_bytes,
+                        void* stream);
+int vad_csv_index(const uint8_t* bytes, int64_t n_bytes, int64_t skip, int64_t base, int64_t* index,
+                  int64_t capacity, const void* ws, size_t ws_bytes, void* stream);
+int vad_csv_parse(const uint8_t* bytes, int64_t n_bytes, const int64_t* index, int64_t n_rows, int64_t base,
+                  int32_t n_cols, const int32_t* columns, int32_t n_used, int32_t out_f64, void* X, uint8_t* y,
+                  int32_t* row_status, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Energy / ZCR / spectral analyser (realtime_analysis/simple_analyzer.py,
  * SimpleAnalyser): per-frame features in fp64, out[f*(3+n_bands) + i]:
  *   0  stEnergy(frame)                    = sum x^2 / frame_len

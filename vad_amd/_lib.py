@@ -26,6 +26,14 @@ FFN_EXACT_F32 = 0
 FFN_SPLIT_F16 = 1
 TREE_WALK_AUTO = 0
 TREE_WALK_GLOBAL = 1
+CSV_TILE = 4096
+CSV_CARRY_PASS = 256
+CSV_MAX_LINE = 4096
+CSV_MAX_COLS = 2048
+CSV_MAX_USED = 1024
+CSV_ROW_HOST = 1
+CSV_ROW_MALFORMED = 2
+CSV_ROW_LABEL = 4
 
 c_i32, c_i64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
 c_int = ctypes.c_int
@@ -71,6 +79,10 @@ SIGNATURES = {
     "vad_scale_workspace_bytes": (c_sz, []),
     "vad_scale_features": (c_int, [c_vp, c_i64, c_i32, c_vp, c_sz, c_vp]),
     "vad_format_csv_rows": (c_i64, [c_vp, c_i64, c_i32, ctypes.c_double, c_vp, c_i64]),
+    "vad_csv_workspace_bytes": (c_sz, [c_i64]),
+    "vad_csv_count_lines": (c_int, [c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "vad_csv_index": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_sz, c_vp]),
+    "vad_csv_parse": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "vad_mfcc_ffn_workspace_bytes": (c_sz, [c_vp, c_vp, c_i64, c_i32, c_i32]),
     "vad_mfcc_ffn": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_sz,
                              c_vp]),

@@ -764,6 +764,42 @@ int64_t vad_format_csv_rows(const float* rows, int64_t n_rows, int32_t n_cols, d
   return format_csv_rows(rows, n_rows, n_cols, label, buf, buf_size);
 }
 
+size_t vad_csv_workspace_bytes(int64_t n_bytes) { return csv_workspace_bytes(n_bytes); }
+
+static bool csv_ws_ok(const void* ws, size_t ws_bytes, int64_t n_bytes) {
+  return ws && reinterpret_cast<uintptr_t>(ws) % 8 == 0 && ws_bytes >= csv_workspace_bytes(n_bytes);
+}
+
+int vad_csv_count_lines(const uint8_t* bytes, int64_t n_bytes, int64_t* n_lines, void* ws, size_t ws_bytes,
+                        void* stream) {
+  if (n_bytes < 0 || n_bytes > (int64_t)1 << 42 || (n_bytes > 0 && !bytes) || !n_lines) return VAD_EINVAL;
+  if (reinterpret_cast<uintptr_t>(n_lines) % 8 || !csv_ws_ok(ws, ws_bytes, n_bytes)) return VAD_EINVAL;
+  return (int)launch_csv_count(bytes, n_bytes, n_lines, ws, (hipStream_t)stream);
+}
+
+int vad_csv_index(const uint8_t* bytes, int64_t n_bytes, int64_t skip, int64_t base, int64_t* index,
+                  int64_t capacity, const void* ws, size_t ws_bytes, void* stream) {
+  if (n_bytes < 0 || n_bytes > (int64_t)1 << 42 || (n_bytes > 0 && !bytes)) return VAD_EINVAL;
+  if (skip < 0 || base < 0 || capacity < 0 || (capacity > 0 && !index)) return VAD_EINVAL;
+  if (reinterpret_cast<uintptr_t>(index) % 8 || !csv_ws_ok(ws, ws_bytes, n_bytes)) return VAD_EINVAL;
+  return (int)launch_csv_index(bytes, n_bytes, skip, base, index, capacity, ws, (hipStream_t)stream);
+}
+
+int vad_csv_parse(const uint8_t* bytes, int64_t n_bytes, const int64_t* index, int64_t n_rows, int64_t base,
+                  int32_t n_cols, const int32_t* columns, int32_t n_used, int32_t out_f64, void* X, uint8_t* y,
+                  int32_t* row_status, void* stream) {
+  if (n_bytes < 0 || n_rows < 0 || base < 0 || n_cols < 2 || n_cols > VAD_CSV_MAX_COLS) return VAD_EINVAL;
+  if (n_used < 1 || n_used > VAD_CSV_MAX_USED || (!columns && n_used != n_cols - 1)) return VAD_EINVAL;
+  for (int j = 0; columns && j < n_used; ++j)
+    if (columns[j] < 0 || columns[j] >= n_cols) return VAD_EINVAL;
+  if (n_rows > 0 && (!bytes || !index || !X || !y || !row_status || n_bytes == 0)) return VAD_EINVAL;
+  if (reinterpret_cast<uintptr_t>(index) % 8 || reinterpret_cast<uintptr_t>(X) % (out_f64 ? 8 : 4) ||
+      reinterpret_cast<uintptr_t>(row_status) % 4)
+    return VAD_EINVAL;
+  return (int)launch_csv_parse(bytes, n_bytes, index, n_rows, base, n_cols, columns, n_used, out_f64 != 0, X, y,
+                               row_status, (hipStream_t)stream);
+}
+
 int vad_features_f32(const float* mfcc, int64_t n_frames, int32_t mfcc_n, int32_t mode,
                      float* features, void* stream) {
   if (n_frames < 0 || mfcc_n <= 0 || mfcc_n > VAD_MAX_MFCC || (mode != 0 && mode != 1))

@@ -206,6 +206,15 @@ size_t scale_workspace_bytes();
 hipError_t launch_scale_features(float* x, int64_t n_rows, int mfcc_n, double* ws, hipStream_t st);
 int64_t format_csv_rows(const float* rows, int64_t n_rows, int n_cols, double label, char* buf,
                         int64_t buf_size);
+// Dataset CSV import (csv_parse_kernel.hip).  The C entries have checked
+// every argument.
+size_t csv_workspace_bytes(int64_t n_bytes);
+hipError_t launch_csv_count(const uint8_t* bytes, int64_t n, int64_t* n_lines, void* ws, hipStream_t st);
+hipError_t launch_csv_index(const uint8_t* bytes, int64_t n, int64_t skip, int64_t base, int64_t* index,
+                            int64_t capacity, const void* ws, hipStream_t st);
+hipError_t launch_csv_parse(const uint8_t* bytes, int64_t n_bytes, const int64_t* index, int64_t n_rows, int64_t base,
+                            int n_cols, const int32_t* columns, int n_used, bool f64, void* x, uint8_t* y,
+                            int32_t* status, hipStream_t st);
 hipError_t launch_tree_rows(const TreeNode* nodes, int n_nodes, const float* x, int64_t n, int dim,
                             uint8_t* labels, hipStream_t st);
 hipError_t launch_tree_windows(const TreeNode* nodes, const TreeNodeC* cnodes, int n_nodes,

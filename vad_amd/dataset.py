@@ -10,6 +10,11 @@ Same functions and argument conventions as the reference modules:
                              ``process_file``, ``create_table_header``,
                              ``write_features``
   dataset/utils.py           ``scale_features``
+  dataset/file_processing.py ``load_csv``, ``features_number``
+  dataset/file_index.py      ``create_file_index``
+  learning/utils.py          ``load_files``
+  dataset/__init__.py        ``random_rows_order`` (the order
+                             random_features_generator draws rows in)
 
 The MFCC / delta features run on the GPU (one clip per call, the offline
 feature rows of ``vad_features_f32``), ``scale_features`` is a device
@@ -17,11 +22,18 @@ reduction (``vad_scale_features``), and the CSV text is produced by a native
 multithreaded formatter (``vad_format_csv_rows``) that prints values exactly
 as numpy prints float32.  ``write_features`` keeps the reference's
 ``csv.writer`` interface.
+
+The way back, CSV text into the float32 ``X`` / uint8 ``y`` the device
+trainers take, is ``read_csv_device``: line index and field parsing are HIP
+kernels (``vad_csv_count_lines`` / ``vad_csv_index`` / ``vad_csv_parse``) that
+give numpy's values bit for bit; the few rows the device does not decide are
+parsed here with ``float()``.
 """
 from __future__ import annotations
 
 import csv
 import ctypes
+import io
 
 import numpy as np
 import torch
@@ -286,3 +298,284 @@ def scale_features(features):
                 fr[g][:] = scaled[i, g * c:(g + 1) * c]
             i += 1
     return features
+
+
+# ----------------------------------------------------------------------------
+# Reading the CSVs back: dataset/file_processing.py:151-242, file_index.py,
+# learning/utils.py, dataset/__init__.py:38-96
+# ----------------------------------------------------------------------------
+CSV_CHUNK_BYTES = 64 << 20  # pinned staging buffer of read_csv_device
+_TORCH_OF = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+
+
+def _csv_source(path_or_bytes):
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        return io.BytesIO(bytes(path_or_bytes))
+    return open(path_or_bytes, "rb")
+
+
+def _after_last_newline(view, n):
+    """One past the last '\n' of view[:n]; 0 when there is none."""
+    hi = n
+    while hi > 0:
+        lo = max(0, hi - (1 << 16))
+        hit = np.flatnonzero(view[lo:hi] == 10)
+        if len(hit):
+            return lo + int(hit[-1]) + 1
+        hi = lo
+    return 0
+
+
+def _csv_chunks(f, chunk_bytes):
+    """Pieces of the file cut after a '\n' (the last one at the end of the
+    file), each as a view of one pinned staging buffer, with the piece's
+    offset in the file.  A line longer than the buffer grows the buffer."""
+    size = max(int(chunk_bytes or CSV_CHUNK_BYTES), 1)
+    stage = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+    view = stage.numpy()
+    filled, base = 0, 0
+    while True:
+        if filled == len(view):  # no line ends in a full buffer
+            bigger = torch.empty(2 * len(view), dtype=torch.uint8, pin_memory=True)
+            bigger.numpy()[:filled] = view[:filled]
+            stage, view = bigger, bigger.numpy()
+        got = f.readinto(memoryview(view)[filled:]) or 0
+        filled += got
+        eof = got == 0
+        if filled == 0:
+            return
+        cut = filled if eof else _after_last_newline(view, filled)
+        if cut == 0:
+            continue
+        yield stage, view, cut, base
+        rest = filled - cut
+        if rest:
+            view[:rest] = view[cut:filled].copy()
+        filled, base = rest, base + cut
+        if eof:
+            return
+
+
+def _line_fields(view, start, end):
+    line = bytes(memoryview(view)[start:end]).decode("latin-1")
+    return line.rstrip("\r\n").split(",")
+
+
+def read_csv_device(path_or_bytes, offset=1, columns_used=None, dtype=torch.float32, device=None,
+                    chunk_bytes=None, max_rows=None):
+    """A dataset CSV (a path, or its bytes) -> ``(X, y, index)`` on the device:
+    X (n_rows, n_used) of ``dtype`` (float32 or float64) with exactly the
+    values of ``np.asarray(csv row, dtype)``, y uint8 =
+    ``int(float(last field))``, index int64 = the byte offset of every data
+    line (``create_file_index``).  ``offset`` lines are skipped first;
+    ``columns_used`` is a list of column indices (default: all but the last).
+    The number of columns is that of the file's first line.
+
+    The file is read through one pinned buffer of ``chunk_bytes`` in pieces
+    cut at line ends, so any file size works; ``max_rows`` stops after that
+    many data rows.  Rows whose text the device does not decide (more than 19
+    significant digits, blanks, ...) are parsed here with ``float()``.
+    ValueError, naming the 1-based line: a row with another number of fields
+    or longer than 4096 bytes, a field ``float()`` refuses, a label outside
+    0..255.  Columns that are not used are not parsed."""
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError("dtype must be torch.float32 or torch.float64")
+    dev = torch.device("cuda" if device is None else device)
+    lib = _lib.lib()
+    cols = None
+    if columns_used is not None and len(columns_used):
+        cols = (ctypes.c_int32 * len(columns_used))(*[int(c) for c in columns_used])
+    np_dtype = np.float32 if dtype == torch.float32 else np.float64
+    skip_left, n_cols, rows_done = int(offset), None, 0
+    Xs, ys, idxs = [], [], []
+    with torch.cuda.device(dev), _csv_source(path_or_bytes) as f:
+        st = _lib.stream_ptr()
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        for stage, view, cut, base in _csv_chunks(f, chunk_bytes):
+            if max_rows is not None and rows_done >= max_rows:
+                break
+            if n_cols is None:  # the file's first line (the header, when there is one)
+                first = bytes(memoryview(view)[:cut]).split(b"\n", 1)[0]
+                n_cols = first.count(b",") + 1
+                if n_cols < 2:
+                    raise ValueError("line 1: a dataset CSV has at least one feature column and a label")
+                if cols is not None and not all(0 <= c < n_cols for c in cols):
+                    raise ValueError(f"columns_used outside the file's {n_cols} columns")
+            d_bytes = torch.empty(cut, dtype=torch.uint8, device=dev)
+            d_bytes.copy_(stage[:cut], non_blocking=True)
+            nb = int(lib.vad_csv_workspace_bytes(cut))
+            ws = torch.empty(nb // 8, dtype=torch.int64, device=dev)
+            _lib.check(lib.vad_csv_count_lines(_lib.ptr(d_bytes), cut, _lib.ptr(count), _lib.ptr(ws), nb, st),
+                       "vad_csv_count_lines")
+            n_lines = int(count.item())  # also: the copy out of the staging buffer is done
+            skip = min(skip_left, n_lines)
+            skip_left -= skip
+            n_rows = n_lines - skip
+            if max_rows is not None:
+                n_rows = min(n_rows, max_rows - rows_done)
+            if n_rows == 0:
+                continue
+            index = torch.empty(n_rows, dtype=torch.int64, device=dev)
+            _lib.check(lib.vad_csv_index(_lib.ptr(d_bytes), cut, skip, base, _lib.ptr(index), n_rows, _lib.ptr(ws),
+                                         nb, st), "vad_csv_index")
+            n_used = len(cols) if cols is not None else n_cols - 1
+            X = torch.empty((n_rows, n_used), dtype=dtype, device=dev)
+            y = torch.empty(n_rows, dtype=torch.uint8, device=dev)
+            status = torch.empty(n_rows, dtype=torch.int32, device=dev)
+            # the text of exactly these rows: the last one ends where the next line starts
+            end = cut
+            if n_rows < n_lines - skip:
+                nxt = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+                _lib.check(lib.vad_csv_index(_lib.ptr(d_bytes), cut, skip, base, _lib.ptr(nxt), n_rows + 1,
+                                             _lib.ptr(ws), nb, st), "vad_csv_index")
+                end = int(nxt[-1].item()) - base
+            _lib.check(lib.vad_csv_parse(_lib.ptr(d_bytes), end, _lib.ptr(index), n_rows, base, n_cols, cols, n_used,
+                                         int(dtype == torch.float64), _lib.ptr(X), _lib.ptr(y), _lib.ptr(status),
+                                         st), "vad_csv_parse")
+            bad = torch.nonzero(status).flatten()
+            if bad.numel():
+                _patch_rows(view, end, base, index, bad, status, X, y, cols, n_cols, np_dtype,
+                            int(offset) + rows_done)
+            Xs.append(X)
+            ys.append(y)
+            idxs.append(index)
+            rows_done += n_rows
+    if not Xs:
+        n_used = len(cols) if cols is not None else max((n_cols or 1) - 1, 0)
+        return (torch.empty((0, n_used), dtype=dtype, device=dev), torch.empty(0, dtype=torch.uint8, device=dev),
+                torch.empty(0, dtype=torch.int64, device=dev))
+    if len(Xs) == 1:
+        return Xs[0], ys[0], idxs[0]
+    return torch.cat(Xs), torch.cat(ys), torch.cat(idxs)
+
+
+def _patch_rows(view, end, base, index, bad, status, X, y, cols, n_cols, np_dtype, lines_before):
+    """The rows the device flagged, parsed as numpy parses them, from the text
+    still in the staging buffer; raises for what numpy refuses."""
+    rows = bad.cpu().numpy()
+    codes = status[bad].cpu().numpy()
+    starts = index[bad].cpu().numpy() - base
+    nxt = torch.clamp(bad + 1, max=index.numel() - 1)
+    ends = np.where(rows + 1 < index.numel(), index[nxt].cpu().numpy() - base, end)
+    used = list(cols) if cols is not None else list(range(n_cols - 1))
+    px = np.empty((len(rows), len(used)), np_dtype)
+    py = np.empty(len(rows), np.uint8)
+    for k, (r, code, a, b) in enumerate(zip(rows, codes, starts, ends)):
+        ln = lines_before + int(r) + 1
+        fields = _line_fields(view, int(a), int(b))
+        if code & _lib.CSV_ROW_MALFORMED:
+            if len(fields) != n_cols:
+                raise ValueError(f"line {ln}: {len(fields)} fields, expected {n_cols}")
+            raise ValueError(f"line {ln}: longer than {_lib.CSV_MAX_LINE} bytes")
+        try:
+            vals = [float(fields[c]) for c in used]
+            label = int(float(fields[-1]))
+        except (ValueError, OverflowError) as e:
+            raise ValueError(f"line {ln}: {e}") from None
+        if not 0 <= label <= 255:
+            raise ValueError(f"line {ln}: label {fields[-1]!r} is outside 0..255")
+        px[k] = np.asarray(vals, np.float64).astype(np_dtype)
+        py[k] = label
+    X[bad] = torch.from_numpy(px).to(X.device)
+    y[bad] = torch.from_numpy(py).to(y.device)
+
+
+def load_csv(fname, items_num, columns_used=None, memmap=False, dtype=np.float32):
+    """file_processing.py:151-184: the first ``items_num`` data rows after the
+    header line as numpy ``features`` (items_num, d) of ``dtype`` and
+    ``results`` (items_num, 1) int32.  ValueError when the file has fewer
+    rows (the reference's ``reader.next()`` raises there too).  ``memmap`` is
+    accepted and unused, as in the reference.  Parsed on the device."""
+    tdt = _TORCH_OF.get(np.dtype(dtype))
+    if tdt is None:
+        raise TypeError("dtype must be float32 or float64")
+    X, y, _ = read_csv_device(fname, 1, list(columns_used) if columns_used is not None else None, tdt,
+                              max_rows=int(items_num))
+    if X.shape[0] < items_num:
+        raise ValueError(f"{fname}: {X.shape[0]} data rows, {items_num} asked for")
+    return X.cpu().numpy(), y.cpu().numpy().astype(np.int32).reshape(-1, 1)
+
+
+def load_files(files, features_num, dtype=np.float64):
+    """learning/utils.py:5-21: ``load_csv`` of every file, concatenated along
+    axis 0 (what the reference plainly meant: its ``np.concatenate`` of a 1-D
+    empty array with a 2-D one raises)."""
+    parts = [load_csv(f, n, dtype=dtype) for f, n in zip(files, features_num)]
+    if not parts:
+        return np.empty((0, 0), dtype), np.empty((0, 1), np.int32)
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+
+def create_file_index(path, offset=1):
+    """file_index.py:7-23: the byte offset of every line after the first
+    ``offset`` lines, uint64; counted and filled on the device."""
+    lib = _lib.lib()
+    dev = torch.device("cuda")
+    out, skip_left = [], int(offset)
+    with _csv_source(path) as f:
+        st = _lib.stream_ptr()
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        for stage, view, cut, base in _csv_chunks(f, None):
+            d_bytes = torch.empty(cut, dtype=torch.uint8, device=dev)
+            d_bytes.copy_(stage[:cut], non_blocking=True)
+            nb = int(lib.vad_csv_workspace_bytes(cut))
+            ws = torch.empty(nb // 8, dtype=torch.int64, device=dev)
+            _lib.check(lib.vad_csv_count_lines(_lib.ptr(d_bytes), cut, _lib.ptr(count), _lib.ptr(ws), nb, st),
+                       "vad_csv_count_lines")
+            n_lines = int(count.item())
+            skip = min(skip_left, n_lines)
+            skip_left -= skip
+            if n_lines == skip:
+                continue
+            index = torch.empty(n_lines - skip, dtype=torch.int64, device=dev)
+            _lib.check(lib.vad_csv_index(_lib.ptr(d_bytes), cut, skip, base, _lib.ptr(index), n_lines - skip,
+                                         _lib.ptr(ws), nb, st), "vad_csv_index")
+            out.append(index.cpu().numpy().astype(np.uint64))
+    return np.concatenate(out) if out else np.asarray([], dtype=np.uint64)
+
+
+def features_number(path):
+    """file_processing.py:231-233: the number of data lines of a dataset CSV
+    (the length of its index; the index is computed, not read from an h5py
+    file)."""
+    return len(create_file_index(path))
+
+
+def random_rows_order(sizes, total_size=1.0, lines_per_block=8, seed=0):
+    """The order in which random_features_generator (dataset/__init__.py:38-96)
+    over create_random_file_gen sources (file_processing.py:214-228) visits
+    rows, as int32 row numbers into the concatenation of the sources (source
+    i's rows start at sum(sizes[:i])), for ``FFNTrainer.steps``.
+
+    Per source ``int(total_size * n_i)`` rows in runs of ``lines_per_block``
+    consecutive rows from uniformly drawn starts (the last run is cut to the
+    count); the sources are interleaved by drawing each next row from a
+    source with probability proportional to the rows it has left, which is a
+    uniform shuffle of the sources' labels.  Same distribution, not numpy's
+    legacy random stream.  Two reference bugs are not kept: its starts are
+    drawn from [0, n_i] inclusive and its runs read past the end of the file;
+    here starts lie in [0, n_i - lines_per_block] (0 for a shorter source)."""
+    rng = np.random.default_rng(seed)
+    lpb = int(lines_per_block)
+    if lpb < 1:
+        raise ValueError("lines_per_block must be positive")
+    seqs, base = [], 0
+    for n in sizes:
+        n = int(n)
+        m = int(total_size * n)
+        if m > 0:
+            run = min(lpb, n)
+            starts = rng.integers(0, n - run + 1, size=-(-m // run))
+            seq = (starts[:, None] + np.arange(run)[None, :]).reshape(-1)[:m] + base
+        else:
+            seq = np.empty(0, np.int64)
+        seqs.append(seq)
+        base += n
+    if base >= 1 << 31:
+        raise ValueError("more than 2^31 rows")
+    labels = np.repeat(np.arange(len(seqs)), [len(s) for s in seqs])
+    rng.shuffle(labels)
+    order = np.empty(len(labels), np.int32)
+    for i, seq in enumerate(seqs):
+        order[labels == i] = seq
+    return order
