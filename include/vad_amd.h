@@ -638,6 +638,81 @@ int vad_gather_active_frames_i16(const int16_t* audio, int64_t n_samples, const 
                                  void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Clip batches: many finished clips of different lengths in one call
+ * (dataset_creator.py:58-71 takes FILES_PER_STEP files at a time; a server
+ * runs vad.py:52-72 over a queue of utterances).  The clips are packed into
+ * one buffer on the hop grid and the clip entries above run ONCE over it:
+ *   clip k (len[k] samples) starts at sample start[k] = hop * frame0[k] and
+ *   occupies ceil(len[k] / hop) hop slots, start[k+1] = start[k] + hop *
+ *   ceil(len[k] / hop); the tail of its last slot is zero.  Frame i of clip
+ *   k is then frame frame0[k] + i of the packed buffer and window (row) i of
+ *   clip k, i < n_rows[k] = max(vad_n_frames(len[k]) - 5, 0), is window
+ *   frame0[k] + i.  Frames that straddle two clips are junk: nothing reads
+ *   their rows.  row0[k] = sum of n_rows before k (rows packed clip after
+ *   clip).
+ * All tables are int64 arrays of n_clips entries in device memory.  Their
+ * CONTENT is the caller's contract (frame0 non-decreasing, ranges disjoint);
+ * whatever they hold, no entry reads or writes outside the arrays it is
+ * given, the sources of vad_batch_pack_* excepted (those addresses are read
+ * as given).
+ *
+ * vad_batch_pack_*: dst[start[k] + i] = (clip k)[i], i < lens[k]; every other
+ * element of dst[0 .. total) = 0.  src_ptrs[k] is the device address of clip
+ * k's first sample as an int64 (aligned to the sample size, otherwise
+ * arbitrary); bits are copied.  dst must be 16-byte aligned.  One kernel
+ * launch whatever n_clips.
+ *
+ * vad_batch_compact_rows: out[row0[k] + i] = rows[frame0[k] + i] for i <
+ * n_rows[k], rows of row_bytes bytes (feature rows: 12 * mfcc_n; labels: 1);
+ * rows has n_rows_in rows, out n_rows_out = sum of n_rows.  out must be
+ * 16-byte aligned and must not overlap rows.
+ * ------------------------------------------------------------------------- */
+int vad_batch_pack_f32(const int64_t* src_ptrs, const int64_t* lens, const int64_t* start, int64_t n_clips,
+                       float* dst, int64_t total, void* stream);
+int vad_batch_pack_i16(const int64_t* src_ptrs, const int64_t* lens, const int64_t* start, int64_t n_clips,
+                       int16_t* dst, int64_t total, void* stream);
+int vad_batch_compact_rows(const void* rows, int64_t n_rows_in, int64_t row_bytes, const int64_t* frame0,
+                           const int64_t* n_rows, const int64_t* row0, int64_t n_clips, void* out,
+                           int64_t n_rows_out, void* stream);
+
+/* Smoothing and segments over the global window array (n labels) of a batch.
+ *   a[w] = (labels[w] == active) if frame0[k] <= w < frame0[k] + n_rows[k] for
+ *   some k, else 0: a window of no clip is never active and never emitted.
+ * close / open / smooth are those of "Speech segments", applied to every
+ * clip's own range as if it were a whole sequence: a run that touches a
+ * clip's first or last window touches an end; no gap closes and no run is
+ * measured across a clip boundary.
+ * vad_batch_label_smooth: out[w] = smooth(max_gap, min_run)(a)[w], 0 / 1.
+ * vad_batch_label_segments: after smooth, close(frame_size / hop - 1) per
+ * clip; each remaining run [i0, i1] of clip k (clip-local windows) is a row of
+ * clip_segments, four int64:
+ *   k, start = (i0+2)*hop, end = min((i1+2)*hop + frame_size, len[k]) in the
+ *   clip's own samples, offset = sum of end - start over the rows before it;
+ * rows ordered by clip, then start.  packed_segments holds the same rows as
+ * three int64 (hop*frame0[k] + start, hop*frame0[k] + end, offset): the table
+ * vad_gather_segments_* takes with the packed buffer as its audio.
+ * counts[0] = rows found, counts[1] = voiced samples of all rows found; only
+ * the first `capacity` rows of either table are written.  Per clip (n_clips
+ * entries each): clip_rows[k] rows, the first of them row clip_row0[k] (the
+ * exclusive prefix of clip_rows), clip_voiced[k] samples.
+ * `ws`: >= vad_batch_segments_workspace_bytes(n, n_clips) bytes, 16-byte
+ * aligned.  VAD_EINVAL: a null table with n_clips > 0, hop outside
+ * (0, frame_size], a negative size, an output overlapping the labels, a
+ * workspace that is too small.  The scans run on tiles of VAD_SEG_TILE
+ * labels, in a fixed chain of launches.
+ * ------------------------------------------------------------------------- */
+size_t vad_batch_segments_workspace_bytes(int64_t n_labels, int64_t n_clips);
+int vad_batch_label_smooth(const uint8_t* labels, int64_t n, const int64_t* frame0, const int64_t* n_rows,
+                           int64_t n_clips, int32_t active, int64_t max_gap, int64_t min_run, uint8_t* out, void* ws,
+                           size_t ws_bytes, void* stream);
+int vad_batch_label_segments(const uint8_t* labels, int64_t n, const int64_t* frame0, const int64_t* n_rows,
+                             const int64_t* len, int64_t n_clips, int32_t active, int64_t max_gap, int64_t min_run,
+                             int32_t frame_size, int32_t hop, int64_t* clip_segments /* capacity x 4 */,
+                             int64_t* packed_segments /* capacity x 3 */, int64_t capacity, int64_t* counts /* 2 */,
+                             int64_t* clip_rows, int64_t* clip_row0, int64_t* clip_voiced, void* ws, size_t ws_bytes,
+                             void* stream);
+
+/* ---------------------------------------------------------------------------
  * Streaming segments: the same segments and voiced samples, online, for the
  * S streams of the hop kernels above (vad.py:32-59 keeps the samples of the
  * active frames while it feeds them).  Per stream the entries consume the

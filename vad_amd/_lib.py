@@ -124,6 +124,13 @@ SIGNATURES = {
                                              c_sz, c_vp]),
     "vad_gather_active_frames_i16": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp,
                                              c_sz, c_vp]),
+    "vad_batch_pack_f32": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "vad_batch_pack_i16": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "vad_batch_compact_rows": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "vad_batch_segments_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "vad_batch_label_smooth": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "vad_batch_label_segments": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32,
+                                         c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vad_stream_seg_delay": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "vad_stream_seg_flush_rows": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "vad_stream_seg_state_bytes": (c_sz, [c_i64]),

@@ -10,6 +10,8 @@ Same functions and argument conventions as the reference modules:
                              ``process_file``, ``create_table_header``,
                              ``write_features``
   dataset/utils.py           ``scale_features``
+  dataset_creator.py:19-73   ``process_files`` (a chunk of files per call:
+                             one clip batch, vad_amd.batch)
   dataset/file_processing.py ``load_csv``, ``features_number``
   dataset/file_index.py      ``create_file_index``
   learning/utils.py          ``load_files``
@@ -298,6 +300,59 @@ def scale_features(features):
                 fr[g][:] = scaled[i, g * c:(g + 1) * c]
             i += 1
     return features
+
+
+# ----------------------------------------------------------------------------
+# dataset_creator.py:19-73
+# ----------------------------------------------------------------------------
+FILES_PER_STEP = 30  # config.py:32
+
+
+def list_audio_files(files, max_files=None):
+    """dataset_creator.py:31-40: the .wav / .sph files of every directory of
+    ``files`` (a file path stands for itself, if it passes the same filter),
+    cut to ``max_files``.  Directory entries are taken in sorted order (the
+    reference takes os.listdir's, which is arbitrary)."""
+    import os
+    todo = []
+    for p in files:
+        names = [p + '/' + f for f in sorted(os.listdir(p))] if os.path.isdir(p) else [p]
+        todo.extend(f for f in names if f.endswith('.wav') or f.endswith('.sph'))
+    if max_files is not None and len(todo) > max_files:
+        todo = todo[:max_files]
+    return todo
+
+
+def process_files(files, files_type, max_files, out, transcription_dir=None, files_per_step=FILES_PER_STEP,
+                  frame_size=400, frame_step=160, fft_n=512, n_filters=26, mfcc_num=13):
+    """dataset_creator.py:19-73: every .wav / .sph file of the directories (or
+    file paths) ``files``, at most ``max_files`` of them, ``files_per_step`` at
+    a time: read and decode on the host (with the transcript
+    ``transcription_dir/<stem>.stm`` when a directory is given), one
+    ``ClipBatch`` and one H2D copy per chunk, the offline feature rows of all
+    its files packed clip after clip, ``scale_features`` over the chunk on the
+    device, one D2H copy, and the CSV text with label ``files_type`` written
+    to ``out`` (a text file object).  Returns the rows written per file."""
+    from .batch import ClipBatch
+    todo = list_audio_files(files, max_files)
+    pipe = _pipeline(frame_size, frame_step, fft_n, n_filters, mfcc_num)
+    counts = []
+    for lo in range(0, len(todo), max(int(files_per_step), 1)):
+        clips = []
+        for path in todo[lo:lo + max(int(files_per_step), 1)]:
+            rate, raw = read_audio(path)
+            if transcription_dir is not None:
+                stem = path.split('/')[-1].split('.')[0]
+                raw = gather_segments(raw, transcription_dir + '/' + stem + '.stm', rate)
+            clips.append(np.ascontiguousarray(np.asarray(raw)))
+        if any(c.dtype != np.int16 for c in clips):  # as file_features: anything but int16 PCM goes in as fp32
+            clips = [c.astype(np.float32) for c in clips]
+        batch = ClipBatch.from_host(clips, pipe.cfg)
+        rows = pipe.features_batch(batch, mode=_lib.FEAT_OFFLINE, packed=True)
+        scale_rows_device(rows)
+        out.write(format_csv_rows(rows.cpu().numpy(), files_type))
+        counts.extend(batch.host["n_rows"].tolist())
+    return counts
 
 
 # ----------------------------------------------------------------------------

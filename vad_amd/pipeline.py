@@ -143,6 +143,65 @@ class VadPipeline:
             stream.synchronize()
         return out[:int(counts[1].item())]
 
+    # -- clip batches (vad_amd.batch.ClipBatch) ------------------------------
+    def _check_batch(self, batch):
+        from .batch import ClipBatch
+        if not isinstance(batch, ClipBatch):
+            raise TypeError("batch must be a ClipBatch")
+        if (batch.frame_size, batch.hop) != (self.cfg.frame_size, self.cfg.hop):
+            raise ValueError(f"the batch is packed for framing {(batch.frame_size, batch.hop)}, the pipeline "
+                             f"frames at {(self.cfg.frame_size, self.cfg.hop)}")
+        if self.cfg.preemph is not None:
+            # pre-emphasis runs along the packed buffer and would carry the last
+            # sample of one clip into the first of the next
+            raise ValueError("cfg.preemph is not supported for clip batches")
+        return batch
+
+    def labels_batch(self, batch, stream=None, fused=False):
+        """The labels of every clip of a ClipBatch from ONE run of labels()
+        over the packed buffer: a BatchLabels whose [k] is the view of clip
+        k's labels, equal to labels(clip k).  FFN (both arithmetic modes) or
+        decision tree; fused=True where ``fusable``.  No synchronisation."""
+        from .batch import BatchLabels
+        self._check_batch(batch)
+        return BatchLabels(self.labels(batch.data, stream=stream, fused=fused), batch)
+
+    def features_batch(self, batch, mode=None, packed=False, stream=None):
+        """The feature rows of every clip of a ClipBatch from one run of
+        features() over the packed buffer.  packed=False: a list of per-clip
+        views of the global rows; packed=True: one contiguous (sum n_rows,
+        3*n_mfcc) tensor, clip after clip (vad_batch_compact_rows)."""
+        from .batch import compact_rows
+        self._check_batch(batch)
+        rows = self.features(batch.data, mode=mode, stream=stream)
+        if packed:
+            return compact_rows(rows, batch, stream=stream)
+        h = batch.host
+        return [rows[f0:f0 + r] for f0, r in zip(h["frame0"].tolist(), h["n_rows"].tolist())]
+
+    def segments_batch(self, batch, max_gap=0, min_run=0, active=1, capacity=None, stream=None):
+        """Speech segments of every clip of a ClipBatch: labels_batch(), then
+        vad_amd.segments.batch_label_segments.  Returns a BatchSegments; no
+        synchronisation."""
+        from .segments import batch_label_segments
+        labels = self.labels_batch(batch, stream=stream)
+        return batch_label_segments(labels, batch, max_gap=max_gap, min_run=min_run, active=active,
+                                    capacity=capacity, stream=stream)
+
+    def voiced_batch(self, batch, max_gap=0, min_run=0, active=1, stream=None):
+        """The voiced samples of every clip of a ClipBatch, packed clip after
+        clip: ``(voiced, offsets)`` with clip k's samples
+        voiced[offsets[k]:offsets[k + 1]] (offsets: (n_clips + 1,) int64
+        numpy).  Synchronises once, as voiced() does."""
+        from .segments import batch_voiced_audio
+        seg = self.segments_batch(batch, max_gap=max_gap, min_run=min_run, active=active, stream=stream)
+        out, _ = batch_voiced_audio(batch, seg, stream=stream)
+        if stream is not None:
+            stream.synchronize()
+        meta = seg.meta.cpu().numpy()
+        offsets = np.concatenate(([0], np.cumsum(meta[2 + 2 * batch.n_clips:]))).astype(np.int64)
+        return out[:int(meta[1])], offsets
+
     def process_clip(self, data):
         """process_file's feature list for an in-memory clip: (F-5, 3, n_mfcc) float64
         (unnormalised, file_processing.py:40-70)."""
