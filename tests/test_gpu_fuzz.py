@@ -632,6 +632,36 @@ def test_fuzz_tree_windows(torch_cuda, depth, offline, F, seed):
     np.testing.assert_array_equal(tree.classes_[got.astype(np.int64)], clf.predict(x))
 
 
+@fuzz(20)
+@given(mfcc_n=st.integers(1, 16), F=st.integers(6, 1500), offline=st.booleans(), depth=st.integers(1, 20),
+       pad=st.booleans(), seed=st.integers(0, 2 ** 32 - 1))
+def test_fuzz_tree_windows_any_width(torch_cuda, mfcc_n, F, offline, depth, pad, seed):
+    """vad_features_tree for MFCC rows of any width 1..16 (13: the compiled
+    width; every other: the runtime-width kernel and its own LDS strides),
+    the table walked from LDS or -- padded with unreachable leaves past the
+    3072 nodes LDS holds -- from global memory: labels equal sklearn's predict
+    on the device's own window features, for trees fitted on them."""
+    import torch
+    from sklearn.tree import DecisionTreeClassifier
+    from vad_amd import _lib
+    from vad_amd import plan as P
+    import tree_tables as T
+    rng = np.random.default_rng(seed)
+    m = torch.from_numpy(T.mfcc_like_rows(F, mfcc_n, seed=int(seed % 10_000))).cuda()
+    mode = _lib.FEAT_OFFLINE if offline else _lib.FEAT_ANALYSER
+    x = P.window_features(m, mode).cpu().numpy()
+    assert x.shape == (F - 5, 3 * mfcc_n)
+    c0 = x[:, 0][~np.isnan(x[:, 0])]  # every window flat (all-NaN column): threshold 0
+    y = rng.integers(0, 2, len(x)) ^ (np.nan_to_num(x[:, 0]) > (np.median(c0) if len(c0) else 0.0)).astype(int)
+    clf = DecisionTreeClassifier(max_depth=depth, random_state=0).fit(x, y)
+    table = O.tree_arrays(clf)
+    assert len(table["feature"]) <= T.LDS_NODES
+    if pad:
+        table = T.pad_table(table, T.LDS_NODES + 1)
+    got = T.classifier(table).window_labels(m, mode).cpu().numpy()
+    np.testing.assert_array_equal(table["classes"][got.astype(np.int64)], clf.predict(x))
+
+
 @fuzz(50)
 @given(L=st.integers(1, 1024), h_frac=st.floats(0.0, 1.0), S=st.integers(1, 300), fpad=st.integers(0, 70),
        hpad=st.integers(0, 70), seed=st.integers(0, 2 ** 32 - 1))

@@ -9,7 +9,8 @@ Three references, none of them the code under test:
     sequence as the hop kernel computed it (the newest ring row after every
     one-hop step): both run feature_triple, explicit-fma code, so the labels
     are equal exactly, for the LDS walk, the global walk and tables on either
-    side of the LDS boundary;
+    side of the LDS boundary (the clip kernel's labels are first checked
+    against the oracle's walk of the device's own feature rows);
   the fp64 oracle, on every window whose path through the tree stays 1e-3
     (the project's analyser-feature tolerance) away from every threshold.
 Every other test is an equivalence between two ways of running the same hops.
@@ -166,11 +167,23 @@ def test_walk_equals_clip_kernel(torch_cuda, S, walk):
     assert (got[:5] == 255).all() and (got[5:] != 255).all()
     clip = _clip_labels(_tree(), seq)
     assert clip.shape == got[5:].shape
+    _assert_clip_equals_host_walk(R.fixture_tree(), clip, seq)
     assert torch.equal(got[5:], clip), int((got[5:] != clip).sum())
     assert torch.equal(got, want_lab)  # auto == global
     assert all(torch.equal(x, y) for x, y in zip((sb.frames, sb.ring, sb.count), state))
     if S == 24:
         assert len(torch.unique(clip)) == 2  # both classes reached
+
+
+def _assert_clip_equals_host_walk(table, clip, seq):
+    """The clip kernel's labels (T - 5, S) against the oracle's walk of the
+    device's own feature rows, every stream: checked before they judge the
+    hop kernel."""
+    from vad_amd.plan import window_features
+    clip = clip.cpu().numpy().astype(np.int64)
+    for s in range(seq.shape[0]):
+        want = O.tree_predict(table, window_features(seq[s].contiguous()).cpu().numpy())
+        assert np.array_equal(table["classes"][clip[:, s]], want), s
 
 
 def _features_of(seq):
@@ -203,6 +216,7 @@ def test_walk_at_the_lds_boundary(torch_cuda, extra):
     assert depth.max() > n_max // 4 and len(set(depth.tolist())) > len(X) // 4  # deep, and both directions taken
     clf = R.classifier(table)
     clip = _clip_labels(clf, seq)
+    _assert_clip_equals_host_walk(table, clip, seq)
     assert len(torch.unique(clip)) == 2  # leaves alternate class along the spine
     dh = torch.from_numpy(hops).cuda()
     out = {}
