@@ -255,14 +255,18 @@ def _device_disassembly(tmp_path):
 
 
 def test_hop_kernel_waits_for_lds_dma_before_barrier(tmp_path):
-    """The hop kernel stages its tables with LDS-DMA (global_load_lds), whose
-    writes count on vmcnt; every workgroup barrier after the DMA must be
-    preceded by a vmcnt(0) wait in the same basic block, or a wave could read
-    a table another wave's DMA has not landed yet (stream_kernel.hip)."""
+    """The hop kernels (FFN and tree: the same staging code in each) stage
+    their tables with LDS-DMA (global_load_lds), whose writes count on
+    vmcnt; every workgroup barrier after the DMA must be preceded by a
+    vmcnt(0) wait in the same basic block, or a wave could read a table
+    another wave's DMA has not landed yet."""
     dis = _device_disassembly(tmp_path)
     funcs = re.split(r"\n(?=[0-9a-f]+ <)", dis)
-    hop = [f for f in funcs if re.match(r"[0-9a-f]+ <_ZN3vad17stream_hop_kernel", f)]
-    assert hop, "stream_hop_kernel not found"
+    hop = []
+    for name in ("_ZN3vad17stream_hop_kernel", "_ZN3vad22stream_hop_tree_kernel"):
+        family = [f for f in funcs if re.match(r"[0-9a-f]+ <" + name, f)]
+        assert family, name + " not found"
+        hop += family
     for f in hop:
         lines = f.splitlines()
         assert any("global_load_lds" in l for l in lines)

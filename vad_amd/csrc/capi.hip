@@ -1058,9 +1058,9 @@ static int stream_hops_entry(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn,
   if (ffn->net.dims[0] > 3 * plan->host.mfcc_n) return VAD_EINVAL;
   if (plan->generic()) return VAD_EUNSUPPORTED;  // its FFT is the 256-point Stockham of fft_n = 512
   if (plan->spec == kSpecWindow) return VAD_EUNSUPPORTED;  // its table blob carries no analysis window
-  return (int)launch_stream_hop(plan->dev, plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps,
-                                ffn->net, frames, frame_stride, frame_len, hop, hop_bytes, hop_stride, hop_len,
-                                n_streams, plan->host.mfcc_n, ring, count, labels, n_hops, hop_block_stride,
+  return (int)launch_stream_hop(plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps, ffn->net,
+                                frames, frame_stride, frame_len, hop, hop_bytes, hop_stride, hop_len, n_streams,
+                                plan->host.mfcc_n, ring, count, labels, n_hops, hop_block_stride,
                                 label_block_stride, (hipStream_t)stream);
 }
 

@@ -85,4 +85,10 @@ __device__ __forceinline__ float window_feature(const float* __restrict__ r0,
   return t == 0 ? ft.mn : t == 1 ? ft.d1 : ft.d2;
 }
 
+// A stream's frame count after one more frame.  The streaming kernels read
+// two things from it, the ring slot c % 5 and "five frames seen" (c >= 5),
+// and 5..9 carry both for any larger count: past 9 it steps back by 5, so it
+// never overflows however long the stream runs.
+__device__ __forceinline__ int ring_count_next(int c) { return (c + 1 >= 10) ? c + 1 - 5 : c + 1; }
+
 }  // namespace vad

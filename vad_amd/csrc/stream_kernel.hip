@@ -12,6 +12,7 @@
 #include "vad_common.h"
 #include "features.h"
 #include "ffn_dev.h"
+#include "stream_hop.h"
 
 namespace vad {
 
@@ -150,44 +151,6 @@ hipError_t launch_preemphasis(const float* x, float* y, int64_t n_rows, int64_t 
 // Lanes within the wave exchange through LDS only (in order per wave): no
 // workgroup barrier anywhere.
 // ---------------------------------------------------------------------------
-// Per-wave LDS scratch (floats): the FFT's ping-pong buffers (the power
-// row reuses the first once the transform is done), the log-mel row, two
-// activation rows.
-#ifndef VAD_HOP_Q
-#define VAD_HOP_Q 4
-#endif
-constexpr int kHopZ = 2 * (256 + 32);              // one 256-point complex buffer, padded
-// complex element i of a buffer sits at i + i / 8: the Stockham stores of the
-// first stages (stride 4 and 16 complex across lanes) spread over the banks
-#ifndef VAD_HOP_PAD
-#define VAD_HOP_PAD 1
-#endif
-__device__ __forceinline__ int zp(int i) { return VAD_HOP_PAD ? i + (i >> 3) : i; }
-constexpr int kHopWaveFloats = 2 * kHopZ + kMaxFilters + 64 + 64;
-
-// Block-shared LDS, staged once per block from the plans (the per-stream
-// chain would otherwise wait on one L2 round trip per tap, DCT term and
-// weight): twiddles, filter ranges and taps, the DCT rows, the FFN weights.
-struct HopTables {
-  const float2* tw;  // W512^k, k < 256
-  const int* f_lo;
-  const int* f_len;
-  const int* f_off;
-  const float* taps;
-  const float* dct;  // [c][m], stride vec_row_stride(nf), 16-B aligned
-  const float* w;    // the FFN weights (FfnDev::wraw: transposed rows)
-};
-
-__device__ __forceinline__ float2 cmulf(float2 a, float2 w) {
-  return make_float2(fmaf(a.x, w.x, -a.y * w.y), fmaf(a.x, w.y, a.y * w.x));
-}
-
-// W256^m, 0 <= m < 256, from the W512^k table
-__device__ __forceinline__ float2 w256(const float2* __restrict__ tw, int m) {
-  const float2 t = tw[2 * (m & 127)];
-  return m < 128 ? t : make_float2(-t.x, -t.y);
-}
-
 // NR: 64-sample chunks of the frame a lane holds (7: frames up to 448
 // samples, the reference's 400; 16: up to 1024) -- the frame and the next
 // hop's samples stay in registers across hops, so the bound matters.
@@ -235,7 +198,7 @@ __global__ __launch_bounds__(1024) void stream_hop_kernel(const float* __restric
   T.f_off = ilo + 2 * nf;
   T.taps = base + ((2 * 256 + 3 * nf + 3) & ~3);  // 16-B aligned rows of n_taps (a multiple of 4) in all
   T.dct = T.taps + n_taps;
-  T.w = base + blob_n;
+  const float* wts = base + blob_n;  // the FFN weights (FfnDev::wraw: transposed rows)
 
   const int64_t s = (int64_t)blockIdx.x * waves + wv;
   const int64_t sc = s < n_streams ? s : 0;
@@ -461,7 +424,7 @@ __global__ __launch_bounds__(1024) void stream_hop_kernel(const float* __restric
         // sums; inputs past din are zero and the weight rows past W_l read
         // the next finite values of the block (zero-padded at its end)
         // the lane's transposed row: four weights per 16-B read
-        const float4* w4 = reinterpret_cast<const float4*>(T.w + net.woff[l] + ln * net.wstride[l]);
+        const float4* w4 = reinterpret_cast<const float4*>(wts + net.woff[l] + ln * net.wstride[l]);
         float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
         if (ln < dout) {
           const float4* h4 = reinterpret_cast<const float4*>(hin);
@@ -474,7 +437,7 @@ __global__ __launch_bounds__(1024) void stream_hop_kernel(const float* __restric
             a3 = fmaf(w.w, h.w, a3);
           }
         }
-        const float acc = T.w[net.boff[l] + (ln < dout ? ln : 0)] + ((a0 + a1) + (a2 + a3));
+        const float acc = wts[net.boff[l] + (ln < dout ? ln : 0)] + ((a0 + a1) + (a2 + a3));
         hout[ln] = ln < dout ? (l + 1 < nl ? relu_nan(acc) : acc) : 0.f;
         float* t = hin;
         hin = hout;
@@ -486,7 +449,7 @@ __global__ __launch_bounds__(1024) void stream_hop_kernel(const float* __restric
       label = (uint8_t)argmax_classes(zl, net.n_classes);
     }
     if (ln == 0) lab_k[s] = label;
-    c = (c + 1 >= 10) ? c + 1 - 5 : c + 1;
+    c = ring_count_next(c);
     asm volatile("" ::: "memory");
   }
   // -- the stream's state back: frame, ring, count
@@ -504,69 +467,24 @@ __global__ __launch_bounds__(1024) void stream_hop_kernel(const float* __restric
 
 template <class TH>
 static hipError_t launch_stream_hop_t(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net,
-                                      float* frames, int64_t fstride, int len, const TH* hop, int64_t hstride,
+                                      float* frames, int64_t fstride, int len, const void* hop, int64_t hstride,
                                       int hlen, int64_t n_streams, int mfcc_n, float* ring, int* count,
                                       uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
                                       hipStream_t st) {
-  if (n_streams <= 0 || n_hops <= 0) return hipSuccess;
-  const size_t tables = (size_t)(blob_n + net.wraw_n) * sizeof(float);
-  // streams per block: at least VAD_HOP_MIN_WAVES (one wave per SIMD), then
-  // spread over every CU (each block stages the ~26 KB of tables from L2
-  // once; the per-stream chain is LDS-bound, so fewer waves per CU run it
-  // faster), up to 16 waves when there are more streams than CUs, and as
-  // many as the LDS holds.  512 streams, A/B on one box: 2 waves per block
-  // on 256 CUs 11.0-11.3 us per hop, 4 on 128 CUs 10.4, 8 on 64 CUs 10.8
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-      n_cu = 256;
-  }
-#ifndef VAD_HOP_MIN_WAVES
-#define VAD_HOP_MIN_WAVES 4
-#endif
-#ifndef VAD_HOP_MIN_WAVES_K
-#define VAD_HOP_MIN_WAVES_K 1  // launches of several hops: the staging amortises over the hops, so
-                               // one stream per block spreads over more CUs (K = 8: 8.2 vs 8.4 us
-                               // per hop, K = 32: 7.4 vs 7.6 with 4 per block)
-#endif
-  int waves = n_hops > 1 ? VAD_HOP_MIN_WAVES_K : VAD_HOP_MIN_WAVES;
-  while (waves < 16 && (int64_t)waves * n_cu < n_streams) waves <<= 1;
-  while (waves > 1 && tables + (size_t)waves * kHopWaveFloats * sizeof(float) > 160 * 1024) waves >>= 1;
-  const size_t smem = tables + (size_t)waves * kHopWaveFloats * sizeof(float);
-  if (smem > 160 * 1024) return hipErrorInvalidValue;
-  static std::atomic<unsigned long long> attr_done{0};  // per hop type: these are the template's own
-  static std::atomic<unsigned long long> attr_done16{0};
-  const bool small = len <= 7 * 64;
-  const void* fn = small ? reinterpret_cast<const void*>(&stream_hop_kernel<7, TH>)
-                         : reinterpret_cast<const void*>(&stream_hop_kernel<16, TH>);
-  const hipError_t e = ensure_dyn_lds(fn, 160 * 1024, small ? attr_done : attr_done16);
-  if (e != hipSuccess) return e;
-  const dim3 grid((unsigned)((n_streams + waves - 1) / waves));
-  if (small)
-    hipLaunchKernelGGL((stream_hop_kernel<7, TH>), grid, dim3(64 * waves), smem, st, blob, blob_n, nf, n_taps, net, frames,
-                       fstride, len, hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride,
-                       lab_kstride);
-  else
-    hipLaunchKernelGGL((stream_hop_kernel<16, TH>), grid, dim3(64 * waves), smem, st, blob, blob_n, nf, n_taps, net, frames,
-                       fstride, len, hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride,
-                       lab_kstride);
-  return hipGetLastError();
+  return launch_hop_kernels<&stream_hop_kernel<7, TH>, &stream_hop_kernel<16, TH>>(
+      (size_t)(blob_n + net.wraw_n) * sizeof(float), len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, net,
+      frames, fstride, len, (const TH*)hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops,
+      hop_kstride, lab_kstride);
 }
 
 // hop: fp32 samples (hop_bytes 4) or int16 PCM (2); strides in elements
-hipError_t launch_stream_hop(const MfccDev* plan, const float* blob, int blob_n, int nf, int n_taps,
-                             const FfnDev& net, float* frames, int64_t fstride, int len, const void* hop,
-                             int hop_bytes, int64_t hstride, int hlen, int64_t n_streams, int mfcc_n, float* ring,
-                             int* count, uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
-                             hipStream_t st) {
-  (void)plan;
-  if (hop_bytes == 2)
-    return launch_stream_hop_t(blob, blob_n, nf, n_taps, net, frames, fstride, len, (const int16_t*)hop, hstride,
-                               hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, st);
-  return launch_stream_hop_t(blob, blob_n, nf, n_taps, net, frames, fstride, len, (const float*)hop, hstride, hlen,
-                             n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, st);
+hipError_t launch_stream_hop(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net, float* frames,
+                             int64_t fstride, int len, const void* hop, int hop_bytes, int64_t hstride, int hlen,
+                             int64_t n_streams, int mfcc_n, float* ring, int* count, uint8_t* labels, int n_hops,
+                             int64_t hop_kstride, int64_t lab_kstride, hipStream_t st) {
+  const auto launch = hop_bytes == 2 ? launch_stream_hop_t<int16_t> : launch_stream_hop_t<float>;
+  return launch(blob, blob_n, nf, n_taps, net, frames, fstride, len, hop, hstride, hlen, n_streams, mfcc_n, ring,
+                count, labels, n_hops, hop_kstride, lab_kstride, st);
 }
 
 }  // namespace vad

@@ -5,12 +5,15 @@
 // stream_hop_tree_kernel is stream_hop_kernel with the FFN replaced by a
 // wave-uniform walk of the tree.  Its front end -- frame shift, 256-point
 // Stockham FFT, real split, mel + log10, lifter x DCT, the ring, the window
-// features -- is a copy of that kernel's code, statement for statement: the
-// FFN hop kernel is the benchmark's and does not move for this one, merging
-// the two is a change with its own A/B, and
+// features -- is a copy of that kernel's code, statement for statement; the
+// LDS layout, the small helpers and the launch rule are shared
+// (stream_hop.h).  One body instantiated by both kernels was built and
+// measured: it kept every register count but not the schedule, and the
+// global walk came out slower (profiles/stream_hop_shared/isa.md), so the
+// copies stay, and
 // tests/test_gpu_stream_tree.py::test_front_end_locked_to_ffn_kernel holds
-// the copies together bit for bit (frames, ring and count of a tree batch
-// and an FFN batch on the same hops).  Change both or neither.
+// them together bit for bit (frames, ring and count of a tree batch and an
+// FFN batch on the same hops).  Change both or neither.
 //
 // The walk: a wave has one window per hop, so every lane would take the same
 // path; the node index is kept uniform (readfirstlane) and each level is one
@@ -22,39 +25,10 @@
 // threshold, tree_walk's rule) -- see launch_stream_hop_tree for the rule.
 #include "vad_common.h"
 #include "features.h"
+#include "stream_hop.h"
 #include "tree_walk.h"
 
 namespace vad {
-namespace {
-
-// -- stream_kernel.hip's per-wave LDS layout and helpers (copies) ------------
-constexpr int kHopZ = 2 * (256 + 32);  // one 256-point complex buffer, padded
-// complex element i of a buffer sits at i + i / 8 (stream_kernel.hip zp)
-__device__ __forceinline__ int zp(int i) { return i + (i >> 3); }
-// the FFT's ping-pong buffers, the log-mel row, two rows of 64: the first
-// holds the window's features (3 mfcc_n <= 48 floats)
-constexpr int kHopWaveFloats = 2 * kHopZ + kMaxFilters + 64 + 64;
-
-struct HopTables {
-  const float2* tw;  // W512^k, k < 256
-  const int* f_lo;
-  const int* f_len;
-  const int* f_off;
-  const float* taps;
-  const float* dct;  // [c][m], stride vec_row_stride(nf), 16-B aligned
-};
-
-__device__ __forceinline__ float2 cmulf(float2 a, float2 w) {
-  return make_float2(fmaf(a.x, w.x, -a.y * w.y), fmaf(a.x, w.y, a.y * w.x));
-}
-
-// W256^m, 0 <= m < 256, from the W512^k table
-__device__ __forceinline__ float2 w256(const float2* __restrict__ tw, int m) {
-  const float2 t = tw[2 * (m & 127)];
-  return m < 128 ? t : make_float2(-t.x, -t.y);
-}
-
-}  // namespace
 
 // NR, TH: as stream_hop_kernel.  lds_nodes: n_nodes when the compact table is
 // staged behind the blob and walked from LDS, 0 for the walk from global.
@@ -311,7 +285,7 @@ __global__ __launch_bounds__(1024) void stream_hop_tree_kernel(
       }
     }
     if (ln == 0) lab_k[s] = (uint8_t)label;
-    c = (c + 1 >= 10) ? c + 1 - 5 : c + 1;
+    c = ring_count_next(c);
     asm volatile("" ::: "memory");
   }
   // -- the stream's state back: frame, ring, count
@@ -331,68 +305,33 @@ __global__ __launch_bounds__(1024) void stream_hop_tree_kernel(
 // largest table walked from LDS is the one that fits beside ONE wave's
 // scratch; a larger one is walked from global memory.
 int64_t stream_tree_max_lds_nodes(int blob_n) {
-  const int64_t room = (int64_t)160 * 1024 - (int64_t)blob_n * sizeof(float) - (int64_t)kHopWaveFloats * sizeof(float);
+  const int64_t room = (int64_t)kHopLdsBytes - (int64_t)blob_n * sizeof(float) - (int64_t)kHopWaveFloats * sizeof(float);
   return room > 0 ? room / (int64_t)sizeof(TreeNodeC) : 0;
 }
 
 template <class TH>
 static hipError_t launch_stream_hop_tree_t(const float* blob, int blob_n, int nf, int n_taps, const TreeNodeC* cnodes,
-                                           const TreeNode* nodes, int n_nodes, bool force_global, float* frames,
-                                           int64_t fstride, int len, const TH* hop, int64_t hstride, int hlen,
+                                           const TreeNode* nodes, int n_nodes, int lds_nodes, float* frames,
+                                           int64_t fstride, int len, const void* hop, int64_t hstride, int hlen,
                                            int64_t n_streams, int mfcc_n, float* ring, int* count, uint8_t* labels,
                                            int n_hops, int64_t hop_kstride, int64_t lab_kstride, hipStream_t st) {
-  if (n_streams <= 0 || n_hops <= 0) return hipSuccess;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-      n_cu = 256;
-  }
-  // waves per block as launch_stream_hop_t chooses them (4 for one hop, 1 for
-  // several, doubled while there are more streams than CUs x waves, up to
-  // 16), then halved until blob + nodes + scratch fit in 160 KiB; the table
-  // leaves LDS only when it does not fit at one wave per block
-  const bool lds = !force_global && cnodes && n_nodes <= stream_tree_max_lds_nodes(blob_n);
-  const int lds_nodes = lds ? n_nodes : 0;
-  const size_t tables = (size_t)blob_n * sizeof(float) + (size_t)lds_nodes * sizeof(TreeNodeC);
-  int waves = n_hops > 1 ? 1 : 4;
-  while (waves < 16 && (int64_t)waves * n_cu < n_streams) waves <<= 1;
-  while (waves > 1 && tables + (size_t)waves * kHopWaveFloats * sizeof(float) > 160 * 1024) waves >>= 1;
-  const size_t smem = tables + (size_t)waves * kHopWaveFloats * sizeof(float);
-  if (smem > 160 * 1024) return hipErrorInvalidValue;
-  static std::atomic<unsigned long long> attr_done{0};  // per hop type: these are the template's own
-  static std::atomic<unsigned long long> attr_done16{0};
-  const bool small = len <= 7 * 64;
-  const void* fn = small ? reinterpret_cast<const void*>(&stream_hop_tree_kernel<7, TH>)
-                         : reinterpret_cast<const void*>(&stream_hop_tree_kernel<16, TH>);
-  const hipError_t e = ensure_dyn_lds(fn, 160 * 1024, small ? attr_done : attr_done16);
-  if (e != hipSuccess) return e;
-  const dim3 grid((unsigned)((n_streams + waves - 1) / waves));
-  if (small)
-    hipLaunchKernelGGL((stream_hop_tree_kernel<7, TH>), grid, dim3(64 * waves), smem, st, blob, blob_n, nf, n_taps,
-                       cnodes, nodes, n_nodes, lds_nodes, frames, fstride, len, hop, hstride, hlen, n_streams, mfcc_n,
-                       ring, count, labels, n_hops, hop_kstride, lab_kstride);
-  else
-    hipLaunchKernelGGL((stream_hop_tree_kernel<16, TH>), grid, dim3(64 * waves), smem, st, blob, blob_n, nf, n_taps,
-                       cnodes, nodes, n_nodes, lds_nodes, frames, fstride, len, hop, hstride, hlen, n_streams, mfcc_n,
-                       ring, count, labels, n_hops, hop_kstride, lab_kstride);
-  return hipGetLastError();
+  return launch_hop_kernels<&stream_hop_tree_kernel<7, TH>, &stream_hop_tree_kernel<16, TH>>(
+      (size_t)blob_n * sizeof(float) + (size_t)lds_nodes * sizeof(TreeNodeC), len, n_streams, n_hops, st, blob, blob_n,
+      nf, n_taps, cnodes, nodes, n_nodes, lds_nodes, frames, fstride, len, (const TH*)hop, hstride, hlen, n_streams,
+      mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride);
 }
 
-// hop: fp32 samples (hop_bytes 4) or int16 PCM (2); strides in elements
+// hop: fp32 samples (hop_bytes 4) or int16 PCM (2); strides in elements.  The
+// table leaves LDS only when it does not fit at one wave per block.
 hipError_t launch_stream_hop_tree(const float* blob, int blob_n, int nf, int n_taps, const TreeNodeC* cnodes,
                                   const TreeNode* nodes, int n_nodes, bool force_global, float* frames,
                                   int64_t fstride, int len, const void* hop, int hop_bytes, int64_t hstride, int hlen,
                                   int64_t n_streams, int mfcc_n, float* ring, int* count, uint8_t* labels, int n_hops,
                                   int64_t hop_kstride, int64_t lab_kstride, hipStream_t st) {
-  if (hop_bytes == 2)
-    return launch_stream_hop_tree_t(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, force_global, frames, fstride,
-                                    len, (const int16_t*)hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels,
-                                    n_hops, hop_kstride, lab_kstride, st);
-  return launch_stream_hop_tree_t(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, force_global, frames, fstride, len,
-                                  (const float*)hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops,
-                                  hop_kstride, lab_kstride, st);
+  const bool lds = !force_global && cnodes && n_nodes <= stream_tree_max_lds_nodes(blob_n);
+  const auto launch = hop_bytes == 2 ? launch_stream_hop_tree_t<int16_t> : launch_stream_hop_tree_t<float>;
+  return launch(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds ? n_nodes : 0, frames, fstride, len, hop,
+                hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -440,7 +379,7 @@ __global__ __launch_bounds__(256) void stream_tree_ring_kernel(const TreeNodeC* 
     const int64_t s = base + tid;
     const int c = count[s];
     labels[s] = c >= 5 ? (uint8_t)tree_walk_c(cnodes, n_nodes, X + tid * kRingXStride) : (uint8_t)255;
-    count[s] = (c + 1 >= 10) ? c + 1 - 5 : c + 1;
+    count[s] = ring_count_next(c);
   }
 }
 

@@ -145,7 +145,7 @@ hipError_t launch_ffn(const FfnDev& net, int src, const float* in, int64_t n_row
                       int mode, uint8_t* labels, hipStream_t st);
 hipError_t launch_stream_ffn(const FfnDev& net, const float* newrow, float* ring, int* count,
                              int64_t n_streams, int mfcc_n, uint8_t* labels, hipStream_t st);
-hipError_t launch_stream_hop(const MfccDev* plan, const float* blob, int blob_n, int nf, int n_taps,
+hipError_t launch_stream_hop(const float* blob, int blob_n, int nf, int n_taps,
                              const FfnDev& net, float* frames, int64_t fstride, int len,
                              const void* hop, int hop_bytes, int64_t hstride, int hlen, int64_t n_streams,
                              int mfcc_n, float* ring, int* count, uint8_t* labels, int n_hops,
