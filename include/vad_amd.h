@@ -455,6 +455,83 @@ int vad_simple_features(const float* frames, int64_t n_frames, int32_t frame_len
                         int32_t n_bands, double* out, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Streams of that analyser: S independent SimpleAnalyser.feed_frame loops
+ * (simple_analyzer.py:78-112, 144-164, 245-256) advanced by a block of K
+ * frames each per call, every stream's state in device memory.
+ *
+ * state: n_streams records of vad_simple_stream_state_bytes(noise_buf_len)
+ * bytes each (8-byte aligned), 1 <= noise_buf_len <= VAD_SIMPLE_MAX_NOISE:
+ *   double noise[noise_buf_len][6]  energy, std|fft|, band 0..3 of the noise
+ *                                   buffer's frames (their feature rows)
+ *   double energy_thresh, spectral_std_thresh, spectral_energy_bands_thresh[4]
+ *   int32  status         the 20-entry status buffer, bit 0 the newest entry
+ *   int32  silence        1 / 0
+ *   int32  noise_pointer
+ *   int32  frame_number   frames fed
+ * vad_simple_stream_init writes a whole record; all other entries read and
+ * update it.
+ *
+ * A feature row is vad_simple_features' with n_bands = 4:
+ * [stEnergy, zcr * frame_len, std|fft|, band 0..3].  The step is the
+ * reference's, update for update: classification with the ZCR window
+ * 5 <= z <= 20 and strict > everywhere else; the status buffer shifted, then
+ * counted; silence off at 5 active entries, on again at 15 inactive ones (that
+ * frame is still labelled active, and joins the noise buffer); thresholds
+ * 0.75 t + 0.25 mean, two products and a sum, never an FMA.  The energy mean
+ * is over energies truncated toward zero to uint32 (:309); an energy of 2^32
+ * or more, where numpy's cast is undefined, saturates to 2^32 - 1.  The std
+ * and band means are summed over the noise rows left to right, in double.
+ *
+ * frames: (K, S, frame_len), frame k of stream s at
+ * frames + k * block_stride + s * stream_stride (elements), samples
+ * contiguous; the frames of a block may not overlap each other (K blocks of
+ * S rows, or S rows of K frames).  fft_len = frame_len + 2 * pad as for
+ * vad_simple_features, 4 * band_bins <= fft_len.  A power-of-two fft_len up
+ * to 4096 runs one kernel (one workgroup per stream); any other fft_len up
+ * to 8193 runs vad_simple_features and then the state steps, takes fp32
+ * frames only and needs features_out as its workspace.
+ *   labels[k * label_block_stride + s] = 1 (active) / 0 (inactive).
+ *   features_out (optional, (K, S, 7) doubles): the rows that were classified.
+ *   voiced / voiced_len (optional, both or neither): voiced + s * voiced_stride
+ *     receives the block's active frames of stream s packed in order (bits
+ *     copied), voiced_len[s] their total length in samples; nothing past it
+ *     is written.  voiced_stride >= n_frames * frame_len.
+ * One or two kernels, no allocation, no synchronisation: capturable.
+ *
+ * VAD_EINVAL before any launch: a null required pointer, n_streams < 1,
+ * n_frames < 0, noise_buf_len outside 1..VAD_SIMPLE_MAX_NOISE, frame_len < 2,
+ * frame_len > 8192, fft_len != frame_len + 2 * pad or > 8193, band_bins < 1,
+ * 4 * band_bins > fft_len, strides under which two frames of a block overlap
+ * in the input or an output (stream_stride < frame_len with n_streams > 1; with
+ * n_frames > 1 overlapping frames or label_block_stride < n_streams;
+ * voiced_stride < n_frames * frame_len with n_streams > 1), voiced without
+ * voiced_len or the reverse, n_frames * frame_len > INT32_MAX, a misaligned state,
+ * int16 frames with an fft_len the one-kernel form does not take, such an
+ * fft_len without features_out.  n_frames == 0: VAD_OK, nothing written.
+ *
+ * vad_simple_stream_state: the state steps alone over feats (K, S, 7).
+ * vad_simple_stream_init: load_init_inactive_frames (:120-138) for every
+ * stream from the rows feats (S, noise_buf_len, 7) of its init frames: noise
+ * buffer, the three thresholds as plain means, status 0, silence 1,
+ * noise_pointer 0, frame_number 0.
+ * ------------------------------------------------------------------------- */
+#define VAD_SIMPLE_MAX_NOISE 64
+size_t vad_simple_stream_state_bytes(int32_t noise_buf_len); /* 0 outside 1..VAD_SIMPLE_MAX_NOISE */
+int vad_simple_stream_init(const double* feats, int64_t n_streams, int32_t noise_buf_len, void* state, void* stream);
+int vad_simple_stream_block_f32(const float* frames, int64_t block_stride, int64_t stream_stride, int32_t frame_len,
+                                int32_t fft_len, int32_t pad, int32_t band_bins, int64_t n_streams, int32_t n_frames,
+                                int32_t noise_buf_len, void* state, uint8_t* labels, int64_t label_block_stride,
+                                double* features_out, float* voiced, int64_t voiced_stride, int32_t* voiced_len,
+                                void* stream);
+int vad_simple_stream_block_i16(const int16_t* frames, int64_t block_stride, int64_t stream_stride, int32_t frame_len,
+                                int32_t fft_len, int32_t pad, int32_t band_bins, int64_t n_streams, int32_t n_frames,
+                                int32_t noise_buf_len, void* state, uint8_t* labels, int64_t label_block_stride,
+                                double* features_out, int16_t* voiced, int64_t voiced_stride, int32_t* voiced_len,
+                                void* stream);
+int vad_simple_stream_state(const double* feats, int64_t n_streams, int32_t n_frames, int32_t noise_buf_len,
+                            void* state, uint8_t* labels, int64_t label_block_stride, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Streaming: S independent analyser streams advanced by one frame each
  * (SKLearnAnalyzer.feed_frame, sklearn_analyser.py:46-82, for S streams at
  * once).  State lives in device buffers the caller allocates with the sizes

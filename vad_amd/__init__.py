@@ -14,3 +14,11 @@ importing a compute entry point without the built library raises.
 from .config import MfccConfig  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # SimpleStreamBatch needs torch and the built library: imported on first use
+    if name == "SimpleStreamBatch":
+        from .simple_stream import SimpleStreamBatch
+        return SimpleStreamBatch
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

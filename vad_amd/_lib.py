@@ -34,6 +34,7 @@ CSV_MAX_USED = 1024
 CSV_ROW_HOST = 1
 CSV_ROW_MALFORMED = 2
 CSV_ROW_LABEL = 4
+SIMPLE_MAX_NOISE = 64
 
 c_i32, c_i64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
 c_int = ctypes.c_int
@@ -76,6 +77,13 @@ SIGNATURES = {
                                c_vp]),
     "vad_simple_features": (c_int, [c_vp, c_i64, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp,
                                     c_vp]),
+    "vad_simple_stream_state_bytes": (c_sz, [c_i32]),
+    "vad_simple_stream_init": (c_int, [c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "vad_simple_stream_block_f32": (c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_i32, c_vp,
+                                            c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "vad_simple_stream_block_i16": (c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_i32, c_vp,
+                                            c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "vad_simple_stream_state": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "vad_scale_workspace_bytes": (c_sz, []),
     "vad_scale_features": (c_int, [c_vp, c_i64, c_i32, c_vp, c_sz, c_vp]),
     "vad_format_csv_rows": (c_i64, [c_vp, c_i64, c_i32, ctypes.c_double, c_vp, c_i64]),

@@ -747,6 +747,94 @@ int vad_simple_features(const float* frames, int64_t n_frames, int32_t frame_len
                                      band_bins, n_bands, out, (hipStream_t)stream);
 }
 
+// Streams of that analyser (simple_stream_kernel.hip): every argument is
+// checked before the first launch.
+size_t vad_simple_stream_state_bytes(int32_t noise_buf_len) {
+  if (noise_buf_len < 1 || noise_buf_len > VAD_SIMPLE_MAX_NOISE) return 0;
+  return (size_t)(6 * noise_buf_len + 6) * sizeof(double) + 4 * sizeof(int32_t);
+}
+
+static bool simple_stream_common_ok(int64_t n_streams, int32_t noise_buf_len, const void* state) {
+  return n_streams >= 1 && vad_simple_stream_state_bytes(noise_buf_len) != 0 && state &&
+         reinterpret_cast<uintptr_t>(state) % 8 == 0;
+}
+
+int vad_simple_stream_init(const double* feats, int64_t n_streams, int32_t noise_buf_len, void* state, void* stream) {
+  if (!simple_stream_common_ok(n_streams, noise_buf_len, state) || !feats) return VAD_EINVAL;
+  return (int)launch_simple_stream_init(feats, n_streams, noise_buf_len, state, (hipStream_t)stream);
+}
+
+int vad_simple_stream_state(const double* feats, int64_t n_streams, int32_t n_frames, int32_t noise_buf_len,
+                            void* state, uint8_t* labels, int64_t label_block_stride, void* stream) {
+  if (!simple_stream_common_ok(n_streams, noise_buf_len, state) || n_frames < 0 || !feats || !labels)
+    return VAD_EINVAL;
+  if (n_frames > 1 && label_block_stride < n_streams) return VAD_EINVAL;
+  if (n_frames == 0) return VAD_OK;
+  return (int)launch_simple_stream_state(feats, n_streams, n_frames, noise_buf_len, state, labels, label_block_stride,
+                                         nullptr, 0, 0, 0, nullptr, 0, nullptr, (hipStream_t)stream);
+}
+
+static int simple_stream_block_entry(const void* frames, int in_bytes, int64_t block_stride, int64_t stream_stride,
+                                     int32_t frame_len, int32_t fft_len, int32_t pad, int32_t band_bins,
+                                     int64_t n_streams, int32_t n_frames, int32_t noise_buf_len, void* state,
+                                     uint8_t* labels, int64_t label_block_stride, double* features_out, void* voiced,
+                                     int64_t voiced_stride, int32_t* voiced_len, void* stream) {
+  if (!simple_stream_common_ok(n_streams, noise_buf_len, state) || n_frames < 0 || !frames || !labels)
+    return VAD_EINVAL;
+  if (frame_len < 2 || frame_len > 8192 || pad < 0 || fft_len != frame_len + 2 * pad || fft_len > 8193)
+    return VAD_EINVAL;
+  if (band_bins < 1 || 4 * (int64_t)band_bins > fft_len) return VAD_EINVAL;  // "FFTN is small"
+  if ((voiced == nullptr) != (voiced_len == nullptr)) return VAD_EINVAL;
+  if ((int64_t)n_frames * frame_len > INT32_MAX) return VAD_EINVAL;
+  if (stream_stride < 0 || (n_streams > 1 && stream_stride < frame_len)) return VAD_EINVAL;
+  if (n_frames > 1) {
+    if (!vad_hop_layout_disjoint(n_streams, n_frames, block_stride, stream_stride, frame_len)) return VAD_EINVAL;
+    if (label_block_stride < n_streams) return VAD_EINVAL;
+  }
+  if (voiced && n_streams > 1 && voiced_stride < (int64_t)n_frames * frame_len) return VAD_EINVAL;
+  const bool one_kernel = simple_stream_block_fits(fft_len);
+  if (!one_kernel && (in_bytes != 4 || !features_out)) return VAD_EINVAL;
+  if (n_frames == 0) return VAD_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (one_kernel)
+    return (int)launch_simple_stream_block(frames, in_bytes, block_stride, stream_stride, frame_len, fft_len, pad,
+                                           band_bins, n_streams, n_frames, noise_buf_len, state, labels,
+                                           label_block_stride, features_out, voiced, voiced_stride, voiced_len, st);
+  // any other length: the rows of every (frame, stream) pair, then the state steps
+  const float* x = static_cast<const float*>(frames);
+  if (n_frames == 1 || block_stride == n_streams * stream_stride) {
+    VAD_TRY(launch_simple_features(x, (int64_t)n_frames * n_streams, frame_len, stream_stride, fft_len, pad,
+                                   band_bins, 4, features_out, st));
+  } else {
+    for (int32_t k = 0; k < n_frames; ++k)
+      VAD_TRY(launch_simple_features(x + k * block_stride, n_streams, frame_len, stream_stride, fft_len, pad,
+                                     band_bins, 4, features_out + (int64_t)k * n_streams * 7, st));
+  }
+  return (int)launch_simple_stream_state(features_out, n_streams, n_frames, noise_buf_len, state, labels,
+                                         label_block_stride, x, block_stride, stream_stride, frame_len,
+                                         static_cast<float*>(voiced), voiced_stride, voiced_len, st);
+}
+
+int vad_simple_stream_block_f32(const float* frames, int64_t block_stride, int64_t stream_stride, int32_t frame_len,
+                                int32_t fft_len, int32_t pad, int32_t band_bins, int64_t n_streams, int32_t n_frames,
+                                int32_t noise_buf_len, void* state, uint8_t* labels, int64_t label_block_stride,
+                                double* features_out, float* voiced, int64_t voiced_stride, int32_t* voiced_len,
+                                void* stream) {
+  return simple_stream_block_entry(frames, 4, block_stride, stream_stride, frame_len, fft_len, pad, band_bins,
+                                   n_streams, n_frames, noise_buf_len, state, labels, label_block_stride,
+                                   features_out, voiced, voiced_stride, voiced_len, stream);
+}
+
+int vad_simple_stream_block_i16(const int16_t* frames, int64_t block_stride, int64_t stream_stride, int32_t frame_len,
+                                int32_t fft_len, int32_t pad, int32_t band_bins, int64_t n_streams, int32_t n_frames,
+                                int32_t noise_buf_len, void* state, uint8_t* labels, int64_t label_block_stride,
+                                double* features_out, int16_t* voiced, int64_t voiced_stride, int32_t* voiced_len,
+                                void* stream) {
+  return simple_stream_block_entry(frames, 2, block_stride, stream_stride, frame_len, fft_len, pad, band_bins,
+                                   n_streams, n_frames, noise_buf_len, state, labels, label_block_stride,
+                                   features_out, voiced, voiced_stride, voiced_len, stream);
+}
+
 size_t vad_scale_workspace_bytes(void) { return scale_workspace_bytes(); }
 
 int vad_scale_features(float* rows, int64_t n_rows, int32_t mfcc_n, void* workspace,

@@ -16,6 +16,7 @@
 // frame (simple_features_wave_kernel, below); otherwise (e.g. 401 samples:
 // L = 513) one 256-thread workgroup per frame with a direct DFT.  Frames of
 // up to 8192 samples: L <= 8192, or 8193 when the pad is odd.
+#include "simple_wave.h"
 #include "vad_common.h"
 
 namespace vad {
@@ -122,18 +123,9 @@ __global__ __launch_bounds__(kSimpleThreads) void simple_features_kernel(
 // Power-of-two L (the reference's 400-sample frames: L = 512): one wave per
 // frame, no workgroup barriers -- the wave's own LDS slice holds its
 // spectrum (LDS operations are in order within a wave), reductions are wave
-// butterflies, and the twiddle table is shared by the workgroup.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
+// butterflies, and the twiddle table is shared by the workgroup.  The wave
+// body is simple_wave.h, shared with simple_stream_kernel.hip.
+//
 // tw_lds: the W_L^j table in LDS (L <= 4096); above, each butterfly computes
 // its twiddle (the 8192-point frame's two 64 KB arrays fill the LDS).
 __global__ __launch_bounds__(kSimpleThreads) void simple_features_wave_kernel(
@@ -157,74 +149,8 @@ __global__ __launch_bounds__(kSimpleThreads) void simple_features_wave_kernel(
   const int n_out = 3 + n_bands;
   const int64_t nw = (int64_t)gridDim.x * waves;
   for (int64_t f = (int64_t)blockIdx.x * waves + wave; f < n_frames; f += nw) {
-    const float* x = frames + f * frame_stride;
-    double e = 0.0, z = 0.0;
-    for (int i = lane; i < frame_len; i += 64) {
-      const double v = (double)x[i];
-      e += v * v;
-      if (i + 1 < frame_len) {
-        const double w = (double)x[i + 1];
-        const double sv = (double)((v > 0.0) - (v < 0.0)), sw = (double)((w > 0.0) - (w < 0.0));
-        z += fabs(sw - sv);
-      }
-    }
-    e = wave_sum(e);
-    z = wave_sum(z);
-    for (int i = lane; i < L; i += 64) {
-      const int sidx = i - pad;
-      const double v = (sidx >= 0 && sidx < frame_len) ? (double)x[sidx] : 0.0;
-      const int r = (int)(__builtin_bitreverse32((unsigned)i) >> (32 - log2L));
-      re[r] = v;
-      im[r] = 0.0;
-    }
-    wave_lds_sync();
-    for (int len = 2; len <= L; len <<= 1) {  // iterative radix-2 DIT, as the block kernel
-      const int half = len >> 1;
-      for (int b = lane; b < (L >> 1); b += 64) {
-        const int grp = b / half, k = b - grp * half;
-        const int i0 = grp * len + k, i1 = i0 + half;
-        const int tw = k * (L / len);
-        double c, s;
-        if (tw_lds) {
-          c = twc[tw];
-          s = tws[tw];
-        } else {
-          sincospi(-2.0 * (double)tw / (double)L, &s, &c);
-        }
-        const double xr = re[i1] * c - im[i1] * s, xi = re[i1] * s + im[i1] * c;
-        const double ar = re[i0], ai = im[i0];
-        re[i0] = ar + xr;
-        im[i0] = ai + xi;
-        re[i1] = ar - xr;
-        im[i1] = ai - xi;
-      }
-      wave_lds_sync();
-    }
-    double mag_sum = 0.0;
-    for (int k = lane; k < L; k += 64) {
-      const double m = sqrt(re[k] * re[k] + im[k] * im[k]);
-      mag_sum += m;
-      re[k] = m;
-    }
-    const double mean = wave_sum(mag_sum) / (double)L;
-    double ssd = 0.0;
-    for (int k = lane; k < L; k += 64) {
-      const double d = re[k] - mean;
-      ssd += d * d;
-    }
-    ssd = wave_sum(ssd);
-    double* o = out + f * n_out;
-    for (int b = 0; b < n_bands; ++b) {
-      double be = 0.0;
-      for (int k = b * band_bins + lane; k < (b + 1) * band_bins; k += 64) be += re[k] * re[k];
-      be = wave_sum(be);
-      if (lane == 0) o[3 + b] = be / (double)band_bins;
-    }
-    if (lane == 0) {
-      o[0] = e / (double)frame_len;
-      o[1] = (z * 0.5) / ((double)frame_len - 1.0) * (double)frame_len;
-      o[2] = sqrt(ssd / (double)L);
-    }
+    simple_wave_features(frames + f * frame_stride, frame_len, L, log2L, pad, band_bins, n_bands, tw_lds, twc, tws,
+                         re, im, lane, out + f * n_out);
     wave_lds_sync();  // the next frame overwrites re / im
   }
 }
