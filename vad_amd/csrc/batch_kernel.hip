@@ -210,11 +210,6 @@ int batch_pack(const int64_t* src_ptrs, const int64_t* lens, const int64_t* star
   return (int)launch_ragged<ES, true>(a, static_cast<hipStream_t>(stream));
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return na && nb && x < y + nb && y < x + na;
-}
-
 }  // namespace
 }  // namespace vad
 

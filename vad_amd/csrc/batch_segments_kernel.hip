@@ -22,58 +22,14 @@
 // first window into clip_rows / clip_row0 / clip_voiced, clips of no windows
 // included (they take the next non-empty clip's row offset).
 // NO KERNEL WAITS ON ANOTHER WORKGROUP: there is no look-back, flag, atomic or
-// grid barrier in this file.  segments_kernel.hip is not touched; the block
-// scan and the carry kernels are repeated here (a few dozen lines) so that
-// the clip path's translation unit stays byte for byte what it was.
-#include "vad_common.h"
+// grid barrier in this file.  The block scan, the two carry kernels
+// (seg_carry_kernel, seg_sum_carry_kernel) and the host helpers are those of
+// the single-clip path, from block_scan.h; the tile kernels are this file's
+// own, because the clip lookup and the clamping sit inside their bodies.
+#include "block_scan.h"
 
 namespace vad {
 namespace {
-
-constexpr int kSegThreads = 256;
-constexpr int kSegItems = 4;
-constexpr int kSegTile = kSegThreads * kSegItems;
-static_assert(kSegTile == VAD_SEG_TILE, "the header's tile is the kernels' tile");
-constexpr int kCarryPass = kSegThreads;
-static_assert(kCarryPass == VAD_SEG_CARRY_PASS, "the header's pass is the carry kernel's pass");
-constexpr int64_t kNone = INT64_MAX;  // "no such window" of a min-scan
-
-struct OpMax {
-  __device__ int64_t operator()(int64_t a, int64_t b) const { return a > b ? a : b; }
-};
-struct OpMin {
-  __device__ int64_t operator()(int64_t a, int64_t b) const { return a < b ? a : b; }
-};
-struct OpSum {
-  __device__ int64_t operator()(int64_t a, int64_t b) const { return a + b; }
-};
-
-// Exclusive scan over the block's 256 threads in thread order (UP) or in
-// reverse thread order (!UP): wave-level __shfl scans, the four wave totals
-// through LDS.  Every LDS word read here was written in the same call.
-template <bool UP, class Op>
-__device__ __forceinline__ int64_t block_excl(int64_t v, Op op, int64_t ident, int64_t* lds, int64_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t t = UP ? __shfl_up(v, d) : __shfl_down(v, d);
-    if (UP ? lane >= d : lane + d < 64) v = op(v, t);
-  }
-  if (lane == (UP ? 63 : 0)) lds[wave] = v;
-  __syncthreads();
-  int64_t pre = ident, tot = ident;
-#pragma unroll
-  for (int w = 0; w < kSegThreads / 64; ++w) {
-    const int64_t x = lds[w];
-    tot = op(tot, x);
-    if (UP ? w < wave : w > wave) pre = op(pre, x);
-  }
-  __syncthreads();  // lds is reused by the next scan
-  int64_t ex = UP ? __shfl_up(v, 1) : __shfl_down(v, 1);
-  if (lane == (UP ? 0 : 63)) ex = ident;
-  *total = tot;
-  return op(pre, ex);
-}
 
 // The clip tables, and the clip of a window.  Whatever the tables hold, a
 // range handed out lies inside [0, n]: the kernels then read no label and
@@ -203,50 +159,6 @@ __global__ __launch_bounds__(kSegThreads) void batch_stage_kernel(StageArgs a) {
   }
 }
 
-// carry_prev[t] = max of tile_last over tiles < t, carry_next[t] = min of
-// tile_first over tiles > t.  One workgroup, kCarryPass tiles per pass.
-__global__ __launch_bounds__(kSegThreads) void batch_carry_kernel(const int64_t* tile_last, const int64_t* tile_first,
-                                                                  int64_t n_tiles, int64_t* carry_prev,
-                                                                  int64_t* carry_next) {
-  __shared__ int64_t lds[kSegThreads / 64];
-  int64_t run = -1, tot;
-  for (int64_t b = 0; b < n_tiles; b += kCarryPass) {
-    const int64_t t = b + threadIdx.x;
-    const int64_t ex = block_excl<true>(t < n_tiles ? tile_last[t] : (int64_t)-1, OpMax(), (int64_t)-1, lds, &tot);
-    if (t < n_tiles) carry_prev[t] = OpMax()(run, ex);
-    run = OpMax()(run, tot);
-  }
-  run = kNone;
-  for (int64_t b = n_tiles > 0 ? (n_tiles - 1) / kCarryPass * kCarryPass : -1; b >= 0; b -= kCarryPass) {
-    const int64_t t = b + threadIdx.x;
-    const int64_t ex = block_excl<false>(t < n_tiles ? tile_first[t] : kNone, OpMin(), kNone, lds, &tot);
-    if (t < n_tiles) carry_next[t] = OpMin()(run, ex);
-    run = OpMin()(run, tot);
-  }
-}
-
-// Exclusive carries of the per-tile row counts and sample sums, and the grand
-// totals into totals[0], totals[1]; n_tiles = 0 writes zero totals.
-__global__ __launch_bounds__(kSegThreads) void batch_sum_carry_kernel(const int64_t* tile_cnt, const int64_t* tile_sum,
-                                                                      int64_t n_tiles, int64_t* carry_cnt,
-                                                                      int64_t* carry_sum, int64_t* totals) {
-  __shared__ int64_t lds[kSegThreads / 64];
-  int64_t run_c = 0, run_s = 0, tot;
-  for (int64_t b = 0; b < n_tiles; b += kCarryPass) {
-    const int64_t t = b + threadIdx.x;
-    const int64_t ec = block_excl<true>(t < n_tiles ? tile_cnt[t] : (int64_t)0, OpSum(), (int64_t)0, lds, &tot);
-    if (t < n_tiles) carry_cnt[t] = run_c + ec;
-    run_c += tot;
-    const int64_t es = block_excl<true>(t < n_tiles ? tile_sum[t] : (int64_t)0, OpSum(), (int64_t)0, lds, &tot);
-    if (t < n_tiles) carry_sum[t] = run_s + es;
-    run_s += tot;
-  }
-  if (threadIdx.x == 0) {
-    totals[0] = run_c;
-    totals[1] = run_s;
-  }
-}
-
 // Segment rows from the final labels d[w] = (w in a clip) && (lab[w] ==
 // active).  A run [i0, i1] of clip k in clip-local windows is the row
 // (k, S(i0), E(i1), offset), S(i) = (i + 2) * hop, E(i) = min((i + 2) * hop +
@@ -372,9 +284,6 @@ __global__ __launch_bounds__(kSegThreads) void batch_clip_finish_kernel(Clips c,
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-inline int64_t n_tiles_of(int64_t n) { return (n + kSegTile - 1) / kSegTile; }
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // workspace: [labels buffer n] [4 tile arrays of int64] [2 clip arrays of int64]
 struct Workspace {
   uint8_t* buf;
@@ -404,21 +313,6 @@ bool ws_ok(const void* ws, size_t ws_bytes, int64_t n, int64_t n_clips) {
   if (n > (int64_t)1 << 40 || n_clips > (int64_t)1 << 40) return false;  // the tile count is a grid dimension
   return ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= workspace_bytes(n, n_clips);
 }
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return na && nb && x < y + nb && y < x + na;
-}
-
-struct Stage {
-  int neg;
-  int64_t g;
-};
-int add_stage(Stage* stages, int k, int neg, int64_t g, int64_t n) {
-  if (g <= 0) return k;  // close(0) and open(m <= 1) change nothing
-  stages[k].neg = neg;
-  stages[k].g = g < n ? g : n;
-  return k + 1;
-}
 
 // The smoothing stages over `labels` into `buf` (always: the windows of no
 // clip must read 0 afterwards, so even no stage is one pass); the result is
@@ -442,7 +336,7 @@ hipError_t run_stages(const uint8_t* labels, const Clips& clips, int active, con
   a.in = labels, a.out = nullptr, a.vin = active, a.reduce = 1, a.neg_next = stages[0].neg;
   batch_stage_kernel<<<dim3((unsigned)nt), dim3(kSegThreads), 0, st>>>(a);
   for (int s = 0; s < n_stages; ++s) {
-    batch_carry_kernel<<<dim3(1), dim3(kSegThreads), 0, st>>>(w.tile[0], w.tile[1], nt, w.tile[2], w.tile[3]);
+    seg_carry_kernel<<<dim3(1), dim3(kSegThreads), 0, st>>>(w.tile[0], w.tile[1], nt, w.tile[2], w.tile[3]);
     a.in = s == 0 ? labels : buf;
     a.vin = s == 0 ? active : 1;
     a.out = buf;
@@ -515,7 +409,7 @@ int vad_batch_label_segments(const uint8_t* labels, int64_t n, const int64_t* fr
   a.rows = clip_segments, a.packed = packed_segments, a.capacity = capacity;
   a.clip_cnt0 = w.clip[0], a.clip_off0 = w.clip[1];
   if (nt > 0) batch_rows_kernel<false><<<dim3((unsigned)nt), dim3(kSegThreads), 0, st>>>(a);
-  batch_sum_carry_kernel<<<dim3(1), dim3(kSegThreads), 0, st>>>(w.tile[0], w.tile[1], nt, w.tile[2], w.tile[3], counts);
+  seg_sum_carry_kernel<true><<<dim3(1), dim3(kSegThreads), 0, st>>>(w.tile[0], w.tile[1], nt, w.tile[2], w.tile[3], counts);
   if (nt > 0) batch_rows_kernel<true><<<dim3((unsigned)nt), dim3(kSegThreads), 0, st>>>(a);
   if (n_clips > 0)
     batch_clip_finish_kernel<<<dim3(1), dim3(kSegThreads), 0, st>>>(clips, w.clip[0], w.clip[1], counts, clip_rows,

@@ -10,8 +10,9 @@
 // launch shape of segments_kernel.hip -- tile kernel (count per tile) ->
 // carry kernel (ONE workgroup looping over the tile counts kCarryPass at a
 // time, which also writes the line total) -> tile kernel (apply: each '\n'
-// stores the offset after it at its rank).  No kernel waits on another
-// workgroup and there are no atomics.
+// stores the offset after it at its rank).  The block scan and the carry loop
+// are block_scan.h's.  No kernel waits on another workgroup and there are no
+// atomics.
 //
 // Parse.  One wave per line, one wave per workgroup (so __syncthreads() is
 // the wave's own ordering point and rows need no packing rule): the wave
@@ -35,48 +36,23 @@
 // blanks, a signed nan and everything outside the grammar set the row's HOST
 // bit, and the caller re-parses that row.  tests/csv_parse_reference.py is
 // this algorithm in Python integers, checked against float().
-#include "vad_common.h"
+#include "block_scan.h"
 #include "pow5_table.h"
 
 namespace vad {
 namespace {
 
 constexpr int kCsvThreads = 256;
+static_assert(kCsvThreads == kScanThreads, "the line index kernels run block_scan.h's scan");
 constexpr int kCsvItems = 16;  // bytes per thread: one 16-byte load
 constexpr int kCsvTile = kCsvThreads * kCsvItems;
 static_assert(kCsvTile == VAD_CSV_TILE, "the header's tile is the kernels' tile");
-constexpr int kCsvCarryPass = kCsvThreads;
-static_assert(kCsvCarryPass == VAD_CSV_CARRY_PASS, "the header's pass is the carry kernel's pass");
+static_assert(kCarryPass == VAD_CSV_CARRY_PASS, "the header's pass is the carry loop's pass");
 constexpr int kMaxLine = VAD_CSV_MAX_LINE;
 constexpr int kMaxCols = VAD_CSV_MAX_COLS;
 constexpr uint64_t kInfBits = 0x7FF0000000000000ull;
 constexpr uint64_t kNanBits = 0x7FF8000000000000ull;
 constexpr int kExpCap = 100000;  // exponent digits saturate here, far past any double
-
-// Exclusive sum over the block's 256 threads in thread order; every LDS word
-// read here was written in the same call.
-__device__ __forceinline__ int64_t block_excl_sum(int64_t v, int64_t* lds, int64_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t t = __shfl_up(v, d);
-    if (lane >= d) v += t;
-  }
-  if (lane == 63) lds[wave] = v;
-  __syncthreads();
-  int64_t pre = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kCsvThreads / 64; ++w) {
-    const int64_t x = lds[w];
-    tot += x;
-    if (w < wave) pre += x;
-  }
-  __syncthreads();  // lds is reused by the next scan
-  int64_t ex = __shfl_up(v, 1);
-  if (lane == 0) ex = 0;
-  *total = tot;
-  return pre + ex;
-}
 
 // Bit j: byte i0 + j is a '\n' that starts a line after it (not the last byte).
 __device__ __forceinline__ uint32_t line_start_bits(const uint8_t* bytes, int64_t n, int64_t i0, bool aligned) {
@@ -101,7 +77,7 @@ __global__ __launch_bounds__(kCsvThreads) void csv_count_kernel(const uint8_t* b
   const bool aligned = (reinterpret_cast<uintptr_t>(bytes) & 15) == 0;
   const int64_t i0 = (int64_t)blockIdx.x * kCsvTile + (int64_t)threadIdx.x * kCsvItems;
   int64_t tot;
-  block_excl_sum(__popc(line_start_bits(bytes, n, i0, aligned)), lds, &tot);
+  block_excl<true>((int64_t)__popc(line_start_bits(bytes, n, i0, aligned)), OpSum(), (int64_t)0, lds, &tot);
   if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
 }
 
@@ -110,9 +86,9 @@ __global__ __launch_bounds__(kCsvThreads) void csv_carry_kernel(const int64_t* t
                                                                 int64_t* carry, int64_t n, int64_t* n_lines) {
   __shared__ int64_t lds[kCsvThreads / 64];
   int64_t run = 0, tot;
-  for (int64_t b = 0; b < n_tiles; b += kCsvCarryPass) {
+  for (int64_t b = 0; b < n_tiles; b += kCarryPass) {
     const int64_t t = b + threadIdx.x;
-    const int64_t ex = block_excl_sum(t < n_tiles ? tile_cnt[t] : (int64_t)0, lds, &tot);
+    const int64_t ex = block_excl<true>(t < n_tiles ? tile_cnt[t] : (int64_t)0, OpSum(), (int64_t)0, lds, &tot);
     if (t < n_tiles) carry[t] = run + ex;
     run += tot;
   }
@@ -128,7 +104,7 @@ __global__ __launch_bounds__(kCsvThreads) void csv_index_kernel(const uint8_t* b
   const int64_t i0 = (int64_t)blockIdx.x * kCsvTile + (int64_t)threadIdx.x * kCsvItems;
   uint32_t m = line_start_bits(bytes, n, i0, aligned);
   int64_t tot;
-  int64_t r = 1 + carry[blockIdx.x] + block_excl_sum(__popc(m), lds, &tot) - skip;
+  int64_t r = 1 + carry[blockIdx.x] + block_excl<true>((int64_t)__popc(m), OpSum(), (int64_t)0, lds, &tot) - skip;
   if (blockIdx.x == 0 && threadIdx.x == 0 && skip == 0 && capacity > 0 && n > 0) index[0] = base;
   while (m) {
     const int j = __ffs(m) - 1;
@@ -387,14 +363,13 @@ __global__ __launch_bounds__(64) void csv_parse_kernel(const CsvParseArgs a) {
 }
 
 inline int64_t csv_tiles(int64_t n) { return (n + kCsvTile - 1) / kCsvTile; }
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 }  // namespace
 
 // workspace: [tile counts] [tile carries], int64 each
 size_t csv_workspace_bytes(int64_t n_bytes) {
   if (n_bytes < 0) return 0;
-  return 2 * align256(sizeof(int64_t) * (size_t)(csv_tiles(n_bytes) + 1));
+  return 2 * align_up(sizeof(int64_t) * (size_t)(csv_tiles(n_bytes) + 1), 256);
 }
 
 hipError_t launch_csv_count(const uint8_t* bytes, int64_t n, int64_t* n_lines, void* ws, hipStream_t st) {

@@ -19,6 +19,8 @@
 // look-back, flag, atomic or grid barrier anywhere in this file.  The carry
 // kernel is ONE workgroup that loops over the tile totals kCarryPass at a
 // time with a running carry, so any tile count works without recursion.
+// The block scan, the carry kernels and the tile constants are in
+// block_scan.h, shared with batch_segments_kernel.hip and the CSV line index.
 //
 // Copy side.  gather_kernel<T, FRAMES>: a persistent grid strides over output
 // tiles of 32 KB below the device-side total; per tile the rows of its first
@@ -28,55 +30,10 @@
 // copied with 8 independent 16-byte stores per lane and the widest loads the
 // source's alignment allows (16, 8, 4 or 2 bytes).  Tiles that straddle rows
 // search per 16-byte destination chunk inside [first row, last row].
-#include "vad_common.h"
+#include "block_scan.h"
 
 namespace vad {
 namespace {
-
-constexpr int kSegThreads = 256;
-constexpr int kSegItems = 4;
-constexpr int kSegTile = kSegThreads * kSegItems;
-static_assert(kSegTile == VAD_SEG_TILE, "the header's tile is the kernels' tile");
-constexpr int kCarryPass = kSegThreads;  // tile totals the carry kernel scans per pass
-static_assert(kCarryPass == VAD_SEG_CARRY_PASS, "the header's pass is the carry kernel's pass");
-constexpr int64_t kNone = INT64_MAX;  // "no such window" of a min-scan
-
-struct OpMax {
-  __device__ int64_t operator()(int64_t a, int64_t b) const { return a > b ? a : b; }
-};
-struct OpMin {
-  __device__ int64_t operator()(int64_t a, int64_t b) const { return a < b ? a : b; }
-};
-struct OpSum {
-  __device__ int64_t operator()(int64_t a, int64_t b) const { return a + b; }
-};
-
-// Exclusive scan over the block's 256 threads in thread order (UP) or in
-// reverse thread order (!UP): wave-level __shfl scans, the four wave totals
-// through LDS.  Every LDS word read here was written in the same call.
-template <bool UP, class Op>
-__device__ __forceinline__ int64_t block_excl(int64_t v, Op op, int64_t ident, int64_t* lds, int64_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t t = UP ? __shfl_up(v, d) : __shfl_down(v, d);
-    if (UP ? lane >= d : lane + d < 64) v = op(v, t);
-  }
-  if (lane == (UP ? 63 : 0)) lds[wave] = v;
-  __syncthreads();
-  int64_t pre = ident, tot = ident;
-#pragma unroll
-  for (int w = 0; w < kSegThreads / 64; ++w) {
-    const int64_t x = lds[w];
-    tot = op(tot, x);
-    if (UP ? w < wave : w > wave) pre = op(pre, x);
-  }
-  __syncthreads();  // lds is reused by the next scan
-  int64_t ex = UP ? __shfl_up(v, 1) : __shfl_down(v, 1);
-  if (lane == (UP ? 0 : 63)) ex = ident;
-  *total = tot;
-  return op(pre, ex);
-}
 
 // One smoothing stage over a tile.  p[i] = (in[i] == vin) != neg; a run of
 // !p is filled (p set) when its length is <= g and it has a p window on both
@@ -158,54 +115,6 @@ __global__ __launch_bounds__(kSegThreads) void seg_stage_kernel(StageArgs a) {
       a.tile_last[tile] = last;
       a.tile_first[tile] = first;
     }
-  }
-}
-
-// Scan of the tile totals of a smoothing stage: carry_prev[t] = max of
-// tile_last over tiles < t, carry_next[t] = min of tile_first over tiles > t.
-// One workgroup, kCarryPass tiles per pass, any n_tiles.
-__global__ __launch_bounds__(kSegThreads) void seg_carry_kernel(const int64_t* tile_last, const int64_t* tile_first,
-                                                                int64_t n_tiles, int64_t* carry_prev,
-                                                                int64_t* carry_next) {
-  __shared__ int64_t lds[kSegThreads / 64];
-  int64_t run = -1, tot;
-  for (int64_t b = 0; b < n_tiles; b += kCarryPass) {
-    const int64_t t = b + threadIdx.x;
-    const int64_t ex = block_excl<true>(t < n_tiles ? tile_last[t] : (int64_t)-1, OpMax(), (int64_t)-1, lds, &tot);
-    if (t < n_tiles) carry_prev[t] = OpMax()(run, ex);
-    run = OpMax()(run, tot);
-  }
-  run = kNone;
-  for (int64_t b = n_tiles > 0 ? (n_tiles - 1) / kCarryPass * kCarryPass : -1; b >= 0; b -= kCarryPass) {
-    const int64_t t = b + threadIdx.x;
-    const int64_t ex = block_excl<false>(t < n_tiles ? tile_first[t] : kNone, OpMin(), kNone, lds, &tot);
-    if (t < n_tiles) carry_next[t] = OpMin()(run, ex);
-    run = OpMin()(run, tot);
-  }
-}
-
-// Scan of per-tile sums (a count, and optionally a second sum): exclusive
-// carries per tile and the grand totals into totals[0] (, totals[1]).  One
-// workgroup looping, as seg_carry_kernel; n_tiles = 0 writes zero totals.
-__global__ __launch_bounds__(kSegThreads) void seg_sum_carry_kernel(const int64_t* tile_cnt, const int64_t* tile_sum,
-                                                                    int64_t n_tiles, int64_t* carry_cnt,
-                                                                    int64_t* carry_sum, int64_t* totals) {
-  __shared__ int64_t lds[kSegThreads / 64];
-  int64_t run_c = 0, run_s = 0, tot;
-  for (int64_t b = 0; b < n_tiles; b += kCarryPass) {
-    const int64_t t = b + threadIdx.x;
-    const int64_t ec = block_excl<true>(t < n_tiles ? tile_cnt[t] : (int64_t)0, OpSum(), (int64_t)0, lds, &tot);
-    if (t < n_tiles) carry_cnt[t] = run_c + ec;
-    run_c += tot;
-    if (tile_sum) {
-      const int64_t es = block_excl<true>(t < n_tiles ? tile_sum[t] : (int64_t)0, OpSum(), (int64_t)0, lds, &tot);
-      if (t < n_tiles) carry_sum[t] = run_s + es;
-      run_s += tot;
-    }
-  }
-  if (threadIdx.x == 0) {
-    totals[0] = run_c;
-    if (tile_sum) totals[1] = run_s;
   }
 }
 
@@ -461,9 +370,6 @@ __global__ __launch_bounds__(kGatherThreads) void gather_kernel(const T* audio, 
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-inline int64_t n_tiles_of(int64_t n) { return (n + kSegTile - 1) / kSegTile; }
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // workspace: [labels buffer n] [4 tile arrays of int64] [window list n int64]
 struct Workspace {
   uint8_t* buf;
@@ -492,15 +398,6 @@ bool ws_ok(const void* ws, size_t ws_bytes, int64_t n) {
   if (n > (int64_t)1 << 40) return false;  // the tile count is a grid dimension
   return ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= workspace_bytes(n);
 }
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return na && nb && x < y + nb && y < x + na;
-}
-
-struct Stage {
-  int neg;
-  int64_t g;
-};
 
 // The smoothing stages over `labels` into `buf`; returns through `cur` /
 // `cur_active` where the result lives: with no effective stage and
@@ -544,13 +441,6 @@ hipError_t run_stages(const uint8_t* labels, int64_t n, int active, const Stage*
   return hipGetLastError();
 }
 
-int add_stage(Stage* stages, int k, int neg, int64_t g, int64_t n) {
-  if (g <= 0) return k;  // close(0) and open(m <= 1) change nothing
-  stages[k].neg = neg;
-  stages[k].g = g < n ? g : n;
-  return k + 1;
-}
-
 template <typename T>
 int gather_segments(const T* audio, int64_t n_samples, const int64_t* segments, const int64_t* counts,
                     int64_t capacity, T* out, int64_t out_capacity, void* stream) {
@@ -592,7 +482,7 @@ int gather_active_frames(const T* audio, int64_t n_samples, const uint8_t* label
   if (nt > 0)
     seg_rank_kernel<false><<<dim3((unsigned)nt), dim3(kSegThreads), 0, st>>>(labels, n, active, w.tile[0], nullptr,
                                                                                nullptr);
-  seg_sum_carry_kernel<<<dim3(1), dim3(kSegThreads), 0, st>>>(w.tile[0], nullptr, nt, w.tile[2], nullptr, count);
+  seg_sum_carry_kernel<false><<<dim3(1), dim3(kSegThreads), 0, st>>>(w.tile[0], nullptr, nt, w.tile[2], nullptr, count);
   const int64_t rows = out_capacity_frames < n ? out_capacity_frames : n;
   if (rows > 0) {
     seg_rank_kernel<true><<<dim3((unsigned)nt), dim3(kSegThreads), 0, st>>>(labels, n, active, nullptr, w.tile[2],
@@ -657,7 +547,7 @@ int vad_label_segments(const uint8_t* labels, int64_t n, int32_t active, int64_t
   a.tile_cnt = w.tile[0], a.tile_sum = w.tile[1], a.carry_cnt = w.tile[2], a.carry_sum = w.tile[3];
   a.rows = segments, a.capacity = capacity;
   if (nt > 0) seg_rows_kernel<false><<<dim3((unsigned)nt), dim3(kSegThreads), 0, st>>>(a);
-  seg_sum_carry_kernel<<<dim3(1), dim3(kSegThreads), 0, st>>>(w.tile[0], w.tile[1], nt, w.tile[2], w.tile[3], counts);
+  seg_sum_carry_kernel<false><<<dim3(1), dim3(kSegThreads), 0, st>>>(w.tile[0], w.tile[1], nt, w.tile[2], w.tile[3], counts);
   if (nt > 0 && capacity > 0) seg_rows_kernel<true><<<dim3((unsigned)nt), dim3(kSegThreads), 0, st>>>(a);
   return (int)hipGetLastError();
 }

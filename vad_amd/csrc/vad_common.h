@@ -263,6 +263,13 @@ inline hipError_t ensure_dyn_lds(const void* fn, int bytes, std::atomic<unsigned
   return e;
 }
 
+// Two byte ranges share a byte (an empty range overlaps nothing): the entries'
+// check of an output against an input.
+inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return na && nb && x < y + nb && y < x + na;
+}
+
 // log10 of a positive energy: native v_log_f32 (with a pre-scale for tiny
 // inputs) times log10(2) -- ~1e-7 relative, far inside the 1e-4 budget.
 __device__ __forceinline__ float log10_pos(float e) {
