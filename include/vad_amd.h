@@ -892,6 +892,84 @@ int vad_stream_segments_flush_i16(int64_t n_streams, int64_t max_gap, int64_t mi
                                   void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Resampling: audio at another rate to the front end's (the mel bank, the
+ * 400 / 160 framing and the classifiers assume 16 kHz; the reference has no
+ * converter, file_processing.py:27-38 hands the file's samples on as they
+ * are).  A polyphase FIR converter for the rational ratio up / down (reduced:
+ * gcd 1), with P = 10 * max(up, down) (0 for 1 / 1) and 2P+1 taps h:
+ *   n_out = ceil(n * up / down)
+ *   y[m]  = sum_j x[j] * h[m * down - j * up + P],   0 <= m < n_out,
+ * x zero outside [0, n): scipy.signal.resample_poly(x, up, down) without the
+ * group delay when h is its default filter (vad_amd/resample.py builds it).
+ * Every output is one fp32 chain x[jmax] * h[r], then fmaf over the T =
+ * ceil((2P+1) / up) taps of its phase in falling j: the same bits from every
+ * entry below.  int16 output: rint (ties to even) saturated to [-32768,
+ * 32767], NaN -> 0.  1 / 1 copies.
+ *
+ * vad_resample_plan_create: `taps` are 2P+1 floats in HOST memory.
+ * VAD_EINVAL: null, up or down <= 0 or not reduced, n_taps != 2P+1, a phase
+ * table of up * (T | 1) floats over VAD_RESAMPLE_MAX_TABLE, or an input tile
+ * ((VAD_RESAMPLE_TILE - 1) * down / up + T samples) over VAD_RESAMPLE_MAX_SPAN
+ * (both live in LDS).  No HIP call: the device copy of the table is made by
+ * vad_resample_plan_upload on the current device, or by the first launch (an
+ * allocation: upload before capturing a launch into a graph).
+ *
+ * vad_resample_batch_<in>_<out>: clip k is lens_in[k] samples at the device
+ * address src_ptrs[k] (aligned to the sample size, otherwise arbitrary);
+ * dst[start[k] + m] = y_k[m] for m < n_out_k, every other element of
+ * dst[0 .. total) = 0: with start / total from the clip-batch placement of
+ * the OUTPUT lengths, dst is a packed clip buffer and needs no pack step.
+ * Tables: int64, n_clips entries, device memory, start non-decreasing (the
+ * clip-batch contract: whatever they hold, nothing is written outside
+ * dst[0 .. total); a clip that passes `total` or the next clip's start is cut
+ * there).  dst must be 16-byte aligned.  One launch whatever n_clips.
+ * src_ptrs[k] == 0 leaves dst[start[k] .. start[k+1]) (.. total for the last
+ * clip) as it is: a buffer of clips at several input rates is filled by one
+ * launch per rate, each with the other rates' addresses zeroed.
+ *
+ * Streams: a hop of hop_out outputs takes hop_in = hop_out * down / up input
+ * samples (VAD_EINVAL when that is no whole number).  With y taken over the
+ * stream's whole input and d = vad_resample_delay = ceil(P / down), the
+ * stream emits z[n] = y[n - d], z[n] = 0 for n < d.  in: element i of hop k of
+ * stream s at in[k * block_stride + s * hop_stride + i], the layouts of
+ * vad_stream_hops; out: (n_hops, n_streams, hop_out) contiguous.  state:
+ * vad_resample_stream_state_bytes bytes, 4-byte aligned, all zero = a stream
+ * before its first sample.  n_hops * hop_in plus the history
+ * (ceil((d * down - P) / up) + T - 1 samples) must fit VAD_RESAMPLE_MAX_SPAN.
+ * ------------------------------------------------------------------------- */
+#define VAD_RESAMPLE_TILE 1024        /* outputs per destination tile */
+#define VAD_RESAMPLE_MAX_TABLE 16384  /* floats of the phase table in LDS (64 KiB) */
+#define VAD_RESAMPLE_MAX_SPAN 16384   /* floats of the input tile / stream window in LDS (64 KiB) */
+typedef struct vad_resample_plan vad_resample_plan;
+int32_t vad_resample_tile_outputs(void);
+int vad_resample_plan_create(int32_t up, int32_t down, const float* taps, int32_t n_taps, vad_resample_plan** out);
+int vad_resample_plan_upload(vad_resample_plan* plan);
+int vad_resample_plan_destroy(vad_resample_plan* plan);
+int64_t vad_resample_n_out(const vad_resample_plan* plan, int64_t n_in); /* -1: bad argument */
+int32_t vad_resample_delay(const vad_resample_plan* plan);
+int vad_resample_batch_f32_f32(vad_resample_plan* plan, const int64_t* src_ptrs, const int64_t* lens_in,
+                               const int64_t* start, int64_t n_clips, float* dst, int64_t total, void* stream);
+int vad_resample_batch_f32_i16(vad_resample_plan* plan, const int64_t* src_ptrs, const int64_t* lens_in,
+                               const int64_t* start, int64_t n_clips, int16_t* dst, int64_t total, void* stream);
+int vad_resample_batch_i16_f32(vad_resample_plan* plan, const int64_t* src_ptrs, const int64_t* lens_in,
+                               const int64_t* start, int64_t n_clips, float* dst, int64_t total, void* stream);
+int vad_resample_batch_i16_i16(vad_resample_plan* plan, const int64_t* src_ptrs, const int64_t* lens_in,
+                               const int64_t* start, int64_t n_clips, int16_t* dst, int64_t total, void* stream);
+size_t vad_resample_stream_state_bytes(const vad_resample_plan* plan, int64_t n_streams);
+int vad_resample_stream_f32_f32(vad_resample_plan* plan, const float* in, int64_t hop_stride, int64_t block_stride,
+                                int64_t n_streams, int32_t n_hops, int32_t hop_out, void* state, float* out,
+                                void* stream);
+int vad_resample_stream_f32_i16(vad_resample_plan* plan, const float* in, int64_t hop_stride, int64_t block_stride,
+                                int64_t n_streams, int32_t n_hops, int32_t hop_out, void* state, int16_t* out,
+                                void* stream);
+int vad_resample_stream_i16_f32(vad_resample_plan* plan, const int16_t* in, int64_t hop_stride, int64_t block_stride,
+                                int64_t n_streams, int32_t n_hops, int32_t hop_out, void* state, float* out,
+                                void* stream);
+int vad_resample_stream_i16_i16(vad_resample_plan* plan, const int16_t* in, int64_t hop_stride, int64_t block_stride,
+                                int64_t n_streams, int32_t n_hops, int32_t hop_out, void* state, int16_t* out,
+                                void* stream);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU clip sharding: one process per GPU, each
  * classifying its shard (vad_amd/dist.py split_clip: windows [w_lo, w_hi)
  * from samples [160 w_lo, 160 (w_hi + 4) + 401)), then ONE collective: the

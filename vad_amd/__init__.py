@@ -21,4 +21,8 @@ def __getattr__(name):
     if name == "SimpleStreamBatch":
         from .simple_stream import SimpleStreamBatch
         return SimpleStreamBatch
+    # the resamplers load the built library on first use
+    if name in ("Resampler", "StreamResampler", "resample_clips", "resample_model", "ResampleSpec"):
+        from . import resample
+        return getattr(resample, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -154,6 +154,17 @@ SIGNATURES = {
                                               c_i64, c_vp, c_vp, c_vp]),
     "vad_stream_segments_flush_i16": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp,
                                               c_i64, c_vp, c_vp, c_vp]),
+    "vad_resample_tile_outputs": (c_i32, []),
+    "vad_resample_plan_create": (c_int, [c_i32, c_i32, c_vp, c_i32, c_vp]),
+    "vad_resample_plan_upload": (c_int, [c_vp]),
+    "vad_resample_plan_destroy": (c_int, [c_vp]),
+    "vad_resample_n_out": (c_i64, [c_vp, c_i64]),
+    "vad_resample_delay": (c_i32, [c_vp]),
+    **{f"vad_resample_batch_{i}_{o}": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp])
+       for i in ("f32", "i16") for o in ("f32", "i16")},
+    "vad_resample_stream_state_bytes": (c_sz, [c_vp, c_i64]),
+    **{f"vad_resample_stream_{i}_{o}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp])
+       for i in ("f32", "i16") for o in ("f32", "i16")},
     "vad_rccl_available": (c_int, []),
     "vad_rccl_error_string": (ctypes.c_char_p, []),
     "vad_rccl_unique_id": (c_int, [c_vp]),

@@ -171,9 +171,13 @@ def _pipeline(frame_size, frame_step, fft_n, n_filters, mfcc_num):
 
 
 def file_features(fname, frame_size=400, frame_step=160, fft_n=512, n_filters=26, mfcc_num=13,
-                  transcription_path=None, device_out=False):
+                  transcription_path=None, device_out=False, resample=False):
     """Feature rows of one file as a (F-5, 3*mfcc_num) float32 array (or a
-    device tensor): process_file's features without the per-row tuples."""
+    device tensor): process_file's features without the per-row tuples.
+    resample: a file at another rate than the front end's is converted on the
+    device (vad_amd.resample) after the transcript's segments were gathered at
+    the file's own rate; False takes its samples as they are, as the
+    reference does."""
     rate, raw = read_audio(fname)
     if transcription_path:
         raw = gather_segments(raw, transcription_path, rate)
@@ -181,6 +185,9 @@ def file_features(fname, frame_size=400, frame_step=160, fft_n=512, n_filters=26
     a = torch.from_numpy(np.ascontiguousarray(np.asarray(raw))).cuda()
     if a.dtype != torch.int16:
         a = a.float()
+    if resample and rate != pipe.cfg.sample_rate:
+        from .resample import Resampler
+        a = Resampler(rate, pipe.cfg.sample_rate)(a)
     feats = _lib_window_features(pipe.mfcc(a), _lib.FEAT_OFFLINE)
     return feats if device_out else feats.cpu().numpy()
 
@@ -190,18 +197,19 @@ def _lib_window_features(mfcc, mode):
     return window_features(mfcc, mode)
 
 
-def process_file(args):
+def process_file(args, resample=False):
     """file_processing.py:14-77 with the same argument list
     [fname, frame_size, frame_step, fft_n, mel_filterbank, mfcc_num,
     counter_queue, transcription_path]: the list of (mfcc, delta1, delta2)
     float64 tuples of the file.  mel_filterbank must be the reference
     filterbank of the (low, high, n_filters) configuration (its row count
-    selects n_filters); counter_queue may be None."""
+    selects n_filters); counter_queue may be None.  resample: see
+    file_features."""
     fname, frame_size, frame_step, fft_n, fbank, mfcc_num = args[:6]
     counter_queue = args[6] if len(args) > 6 else None
     transcription_path = args[7] if len(args) > 7 else None
     f = file_features(fname, frame_size, frame_step, fft_n, int(np.asarray(fbank).shape[0]),
-                      mfcc_num, transcription_path).astype(np.float64)
+                      mfcc_num, transcription_path, resample=resample).astype(np.float64)
     c = mfcc_num
     features = [(r[:c], r[c:2 * c], r[2 * c:]) for r in f]
     if counter_queue is not None:
@@ -324,7 +332,7 @@ def list_audio_files(files, max_files=None):
 
 
 def process_files(files, files_type, max_files, out, transcription_dir=None, files_per_step=FILES_PER_STEP,
-                  frame_size=400, frame_step=160, fft_n=512, n_filters=26, mfcc_num=13):
+                  frame_size=400, frame_step=160, fft_n=512, n_filters=26, mfcc_num=13, resample=False):
     """dataset_creator.py:19-73: every .wav / .sph file of the directories (or
     file paths) ``files``, at most ``max_files`` of them, ``files_per_step`` at
     a time: read and decode on the host (with the transcript
@@ -332,22 +340,32 @@ def process_files(files, files_type, max_files, out, transcription_dir=None, fil
     ``ClipBatch`` and one H2D copy per chunk, the offline feature rows of all
     its files packed clip after clip, ``scale_features`` over the chunk on the
     device, one D2H copy, and the CSV text with label ``files_type`` written
-    to ``out`` (a text file object).  Returns the rows written per file."""
+    to ``out`` (a text file object).  Returns the rows written per file.
+    resample: a chunk with a file at another rate than the front end's is
+    converted on the device into the packed buffer (one launch per distinct
+    rate, vad_amd.resample.resample_clips), after the transcript's segments
+    were gathered at each file's own rate; False (the default) takes every
+    file's samples as they are, as the reference does."""
     from .batch import ClipBatch
     todo = list_audio_files(files, max_files)
     pipe = _pipeline(frame_size, frame_step, fft_n, n_filters, mfcc_num)
     counts = []
     for lo in range(0, len(todo), max(int(files_per_step), 1)):
-        clips = []
+        clips, rates = [], []
         for path in todo[lo:lo + max(int(files_per_step), 1)]:
             rate, raw = read_audio(path)
+            rates.append(int(rate))
             if transcription_dir is not None:
                 stem = path.split('/')[-1].split('.')[0]
                 raw = gather_segments(raw, transcription_dir + '/' + stem + '.stm', rate)
             clips.append(np.ascontiguousarray(np.asarray(raw)))
         if any(c.dtype != np.int16 for c in clips):  # as file_features: anything but int16 PCM goes in as fp32
             clips = [c.astype(np.float32) for c in clips]
-        batch = ClipBatch.from_host(clips, pipe.cfg)
+        if resample and any(r != pipe.cfg.sample_rate for r in rates):
+            from .resample import resample_clips
+            batch = resample_clips(clips, rates, pipe.cfg)
+        else:
+            batch = ClipBatch.from_host(clips, pipe.cfg)
         rows = pipe.features_batch(batch, mode=_lib.FEAT_OFFLINE, packed=True)
         scale_rows_device(rows)
         out.write(format_csv_rows(rows.cpu().numpy(), files_type))

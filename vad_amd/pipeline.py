@@ -91,9 +91,29 @@ class VadPipeline:
             self._ws[key] = ws
         return ws
 
-    def labels(self, audio, out=None, stream=None, fused=False):
+    def _at_rate(self, audio, rate, stream=None):
+        """The clip at cfg.sample_rate: ``audio`` itself when rate is None or
+        that rate, else its float32 conversion (vad_amd.resample)."""
+        if rate is None or rate == self.cfg.sample_rate:
+            return audio
+        from .resample import resample_clips
+        b = resample_clips([audio], rate, self.cfg, stream=stream)
+        return b.data[:int(b.host["len"][0])]
+
+    def _batch_at_rate(self, batch, rate, stream=None):
+        """rate None: the ClipBatch as given; else ``batch`` is a sequence of
+        clips (device tensors or host arrays) at ``rate`` (one rate or one per
+        clip), converted into a ClipBatch at cfg.sample_rate."""
+        if rate is None:
+            return batch
+        from .resample import resample_clips
+        return resample_clips(batch, rate, self.cfg, stream=stream)
+
+    def labels(self, audio, out=None, stream=None, fused=False, rate=None):
         """uint8 (F-5,) labels of every window of a device clip; float32
         samples, or int16 PCM as read from a wav file (identical labels).
+        rate: the clip's sample rate when it is not cfg.sample_rate; the clip
+        is then converted on the device first (None: taken as it is).
         fused=False: MFCC kernel + window kernel through a cached workspace
         (the faster form); fused=True: the single fused kernel, MFCC rows kept
         on chip (vad_mfcc_ffn with no workspace) -- identical labels."""
@@ -102,6 +122,7 @@ class VadPipeline:
         if not (isinstance(audio, torch.Tensor) and audio.is_cuda
                 and audio.dtype in (torch.float32, torch.int16) and audio.is_contiguous()):
             raise TypeError("audio must be a contiguous float32 or int16 CUDA tensor")
+        audio = self._at_rate(audio, rate, stream)
         rows = max(self.n_frames(audio.numel()) - 5, 0)
         if out is None:
             out = torch.empty((rows,), dtype=torch.uint8, device=audio.device)
@@ -121,22 +142,25 @@ class VadPipeline:
             _lib.ptr(ws), 0 if ws is None else ws.numel(), _lib.stream_ptr(stream)), fn)
         return out
 
-    def segments(self, audio, max_gap=0, min_run=0, active=1, capacity=None, stream=None):
+    def segments(self, audio, max_gap=0, min_run=0, active=1, capacity=None, stream=None, rate=None):
         """Speech segments of a device clip: labels(), then
         vad_amd.segments.label_segments at the pipeline's framing (max_gap /
-        min_run in windows).  Returns a Segments; no synchronisation."""
+        min_run in windows).  Returns a Segments; no synchronisation.  With
+        ``rate`` the segments are in samples of the converted clip."""
         from .segments import label_segments
+        audio = self._at_rate(audio, rate, stream)
         labels = self.labels(audio, stream=stream)
         return label_segments(labels, audio.numel(), self.cfg.frame_size, self.cfg.hop, max_gap=max_gap,
                               min_run=min_run, active=active, capacity=capacity, stream=stream)
 
-    def voiced(self, audio, max_gap=0, min_run=0, active=1, stream=None):
+    def voiced(self, audio, max_gap=0, min_run=0, active=1, stream=None, rate=None):
         """The voiced samples of a device clip (float32 or int16, bits
         copied), packed in order: segments(), then the device gather.  The
         result is trimmed to the voiced count, which lives on the device, so
         this call synchronises once (vad_amd.segments.voiced_audio is the form
-        that does not)."""
+        that does not).  With ``rate`` they are samples of the converted clip."""
         from .segments import voiced_audio
+        audio = self._at_rate(audio, rate, stream)
         seg = self.segments(audio, max_gap=max_gap, min_run=min_run, active=active, stream=stream)
         out, counts = voiced_audio(audio, seg, stream=stream)
         if stream is not None:
@@ -157,12 +181,16 @@ class VadPipeline:
             raise ValueError("cfg.preemph is not supported for clip batches")
         return batch
 
-    def labels_batch(self, batch, stream=None, fused=False):
+    def labels_batch(self, batch, stream=None, fused=False, rate=None):
         """The labels of every clip of a ClipBatch from ONE run of labels()
         over the packed buffer: a BatchLabels whose [k] is the view of clip
         k's labels, equal to labels(clip k).  FFN (both arithmetic modes) or
-        decision tree; fused=True where ``fusable``.  No synchronisation."""
+        decision tree; fused=True where ``fusable``.  No synchronisation.
+        rate (here and in the other _batch forms): ``batch`` is then a
+        sequence of clips at that rate, or at one rate each, converted into a
+        ClipBatch on the device first (vad_amd.resample.resample_clips)."""
         from .batch import BatchLabels
+        batch = self._batch_at_rate(batch, rate, stream)
         self._check_batch(batch)
         return BatchLabels(self.labels(batch.data, stream=stream, fused=fused), batch)
 
@@ -179,21 +207,23 @@ class VadPipeline:
         h = batch.host
         return [rows[f0:f0 + r] for f0, r in zip(h["frame0"].tolist(), h["n_rows"].tolist())]
 
-    def segments_batch(self, batch, max_gap=0, min_run=0, active=1, capacity=None, stream=None):
+    def segments_batch(self, batch, max_gap=0, min_run=0, active=1, capacity=None, stream=None, rate=None):
         """Speech segments of every clip of a ClipBatch: labels_batch(), then
         vad_amd.segments.batch_label_segments.  Returns a BatchSegments; no
         synchronisation."""
         from .segments import batch_label_segments
+        batch = self._batch_at_rate(batch, rate, stream)
         labels = self.labels_batch(batch, stream=stream)
         return batch_label_segments(labels, batch, max_gap=max_gap, min_run=min_run, active=active,
                                     capacity=capacity, stream=stream)
 
-    def voiced_batch(self, batch, max_gap=0, min_run=0, active=1, stream=None):
+    def voiced_batch(self, batch, max_gap=0, min_run=0, active=1, stream=None, rate=None):
         """The voiced samples of every clip of a ClipBatch, packed clip after
         clip: ``(voiced, offsets)`` with clip k's samples
         voiced[offsets[k]:offsets[k + 1]] (offsets: (n_clips + 1,) int64
         numpy).  Synchronises once, as voiced() does."""
         from .segments import batch_voiced_audio
+        batch = self._batch_at_rate(batch, rate, stream)
         seg = self.segments_batch(batch, max_gap=max_gap, min_run=min_run, active=active, stream=stream)
         out, _ = batch_voiced_audio(batch, seg, stream=stream)
         if stream is not None:
