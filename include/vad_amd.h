@@ -790,6 +790,91 @@ int vad_batch_label_segments(const uint8_t* labels, int64_t n, const int64_t* fr
                              void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Speech scores: an operating point for the classifiers.  Every entry above
+ * ends in a hard label; here a window gets a score s[i], an fp32 value in
+ * [0, 1] that estimates how likely window i is of class `active`, and labels
+ * are decided from the scores with an onset and an offset threshold, padded,
+ * and scored against a reference.  Nothing here changes what the entries above
+ * compute.  All pointers are device memory; no entry synchronises.
+ *
+ * Scores
+ *   vad_scores_from_logits: from the logits vad_features_ffn_logits writes
+ *     (n rows of n_classes <= VAD_SCORE_MAX_CLASSES floats),
+ *       s = 1 / (1 + sum over j != active of expf(z_j - z_active)),
+ *     every operation in fp32; a row with any non-finite logit scores 0.
+ *     scores must not overlap logits.
+ *   vad_features_tree_scores / vad_tree_predict_scores: the walks of
+ *     vad_features_tree / vad_tree_predict (same features, same comparison,
+ *     same leaf), writing node_score[leaf node] in place of the leaf's class.
+ *     node_score: one float per node of the plan, in the plan's node order
+ *     (for sklearn's predict_proba: value[node][active] / sum(value[node])).
+ *
+ * Decisions (uint8 0 / 1; the segment entries take them with active = 1)
+ *   vad_score_labels (hysteresis): h[-1] = 0 and
+ *       h[i] = 1 if s[i] >= on;  h[i] = 0 if s[i] < off or s[i] is NaN;
+ *       h[i] = h[i-1] otherwise.
+ *     0 <= off <= on <= 1, else VAD_EINVAL (NaN thresholds too).
+ *   vad_label_dilate (padding): out[i] = 1 iff labels[j] == active for some j
+ *     in [i - pad_after, i + pad_before] inside the array: every active run
+ *     grows by pad_before windows at its start and pad_after at its end.
+ *     Any pad >= 0.
+ *   vad_batch_score_labels / vad_batch_label_dilate: the same over the global
+ *     window array of a clip batch ("Clip batches"), every clip's range a
+ *     sequence of its own: h is 0 before a clip's first window, padding stops
+ *     at a clip's first and last window, a window of no clip is 0.
+ *   out must not overlap the input.  `ws`: >= vad_scores_workspace_bytes(n)
+ *   bytes, 16-byte aligned, overlapping neither array (NULL for n == 0).  Each
+ *   is a fixed chain of three launches over tiles of VAD_SEG_TILE windows.
+ *
+ * Scoring against a reference
+ *   vad_reference_labels: `intervals` holds n_intervals rows (start, end) of
+ *     int64, speech [start, end) in samples, ascending and disjoint.  Window i
+ *     (frame i + 2) has the centre sample c = (i+2)*hop + frame_size/2 (integer
+ *     division); out[i] = 1 iff start <= c < end for some row.
+ *   vad_batch_reference_labels: rows (clip, start, end) in the clip's own
+ *     samples, ordered by clip, then start; clip k's rows are
+ *     [clip_row0[k], clip_row0[k+1]) (the last clip's: up to n_intervals), its
+ *     windows frame0[k] + i, i < n_rows[k]; a window of no clip is 0.
+ *   vad_score_histogram_f32: hist[r*bins + b] += the windows with ref[i] == r
+ *     (r = 0, 1; any other ref is not counted) and
+ *       b = min((int)(s[i] * bins), bins - 1) (the product in fp32; a NaN or
+ *       negative product: bin 0),  1 <= bins <= VAD_SCORE_MAX_BINS.
+ *     hist: 2 * bins int64, ZEROED BY THE CALLER (counts are added); the result
+ *     does not depend on the order of the additions.
+ *   vad_score_histogram_u8: the same with b = labels[i] (a label >= n_values
+ *     is not counted), n_values <= 256: the confusion matrix.
+ * ------------------------------------------------------------------------- */
+#define VAD_SCORE_MAX_CLASSES 8
+#define VAD_SCORE_MAX_BINS 4096
+int vad_scores_from_logits(const float* logits, int64_t n, int32_t n_classes, int32_t active, float* scores,
+                           void* stream);
+int vad_features_tree_scores(const vad_tree_plan* tree, const float* node_score, const float* mfcc, int64_t n_frames,
+                             int32_t mfcc_n, int32_t mode, float* scores /* n_frames - 5 */, void* stream);
+int vad_tree_predict_scores(const vad_tree_plan* tree, const float* node_score, const float* x, int64_t n,
+                            float* scores, void* stream);
+size_t vad_scores_workspace_bytes(int64_t n);
+int vad_score_labels(const float* scores, int64_t n, float on, float off, uint8_t* out, void* ws, size_t ws_bytes,
+                     void* stream);
+int vad_label_dilate(const uint8_t* labels, int64_t n, int32_t active, int64_t pad_before, int64_t pad_after,
+                     uint8_t* out, void* ws, size_t ws_bytes, void* stream);
+int vad_batch_score_labels(const float* scores, int64_t n, const int64_t* frame0, const int64_t* n_rows,
+                           int64_t n_clips, float on, float off, uint8_t* out, void* ws, size_t ws_bytes,
+                           void* stream);
+int vad_batch_label_dilate(const uint8_t* labels, int64_t n, const int64_t* frame0, const int64_t* n_rows,
+                           int64_t n_clips, int32_t active, int64_t pad_before, int64_t pad_after, uint8_t* out,
+                           void* ws, size_t ws_bytes, void* stream);
+int vad_reference_labels(const int64_t* intervals /* n_intervals x 2 */, int64_t n_intervals, int64_t n,
+                         int32_t frame_size, int32_t hop, uint8_t* out, void* stream);
+int vad_batch_reference_labels(const int64_t* intervals /* n_intervals x 3 */, int64_t n_intervals,
+                               const int64_t* clip_row0, const int64_t* frame0, const int64_t* n_rows,
+                               int64_t n_clips, int64_t n, int32_t frame_size, int32_t hop, uint8_t* out,
+                               void* stream);
+int vad_score_histogram_f32(const float* scores, const uint8_t* ref, int64_t n, int32_t bins,
+                            int64_t* hist /* 2 x bins */, void* stream);
+int vad_score_histogram_u8(const uint8_t* labels, const uint8_t* ref, int64_t n, int32_t n_values,
+                           int64_t* hist /* 2 x n_values */, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Streaming segments: the same segments and voiced samples, online, for the
  * S streams of the hop kernels above (vad.py:32-59 keeps the samples of the
  * active frames while it feeds them).  Per stream the entries consume the

@@ -25,4 +25,10 @@ def __getattr__(name):
     if name in ("Resampler", "StreamResampler", "resample_clips", "resample_model", "ResampleSpec"):
         from . import resample
         return getattr(resample, name)
+    # the score entries load the built library on first use
+    if name in ("score_labels", "dilate_labels", "batch_score_labels", "batch_dilate_labels", "reference_labels",
+                "batch_reference_labels", "histogram", "confusion", "roc", "roc_from_histogram", "threshold_at",
+                "scores_from_logits", "BatchScores", "Roc"):
+        from . import scores
+        return getattr(scores, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

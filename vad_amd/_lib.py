@@ -35,9 +35,11 @@ CSV_ROW_HOST = 1
 CSV_ROW_MALFORMED = 2
 CSV_ROW_LABEL = 4
 SIMPLE_MAX_NOISE = 64
+SCORE_MAX_CLASSES = 8
+SCORE_MAX_BINS = 4096
 
 c_i32, c_i64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
-c_int = ctypes.c_int
+c_int, c_f32 = ctypes.c_int, ctypes.c_float
 
 # name -> (restype, argtypes); every symbol include/vad_amd.h declares
 SIGNATURES = {
@@ -139,6 +141,19 @@ SIGNATURES = {
     "vad_batch_label_smooth": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "vad_batch_label_segments": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32,
                                          c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vad_scores_from_logits": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "vad_features_tree_scores": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "vad_tree_predict_scores": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "vad_scores_workspace_bytes": (c_sz, [c_i64]),
+    "vad_score_labels": (c_int, [c_vp, c_i64, c_f32, c_f32, c_vp, c_vp, c_sz, c_vp]),
+    "vad_label_dilate": (c_int, [c_vp, c_i64, c_i32, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "vad_batch_score_labels": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_f32, c_f32, c_vp, c_vp, c_sz, c_vp]),
+    "vad_batch_label_dilate": (c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_vp, c_vp, c_sz,
+                                       c_vp]),
+    "vad_reference_labels": (c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "vad_batch_reference_labels": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "vad_score_histogram_f32": (c_int, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "vad_score_histogram_u8": (c_int, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "vad_stream_seg_delay": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "vad_stream_seg_flush_rows": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "vad_stream_seg_state_bytes": (c_sz, [c_i64]),

@@ -734,6 +734,33 @@ int vad_features_tree(const vad_tree_plan* t, const float* mfcc, int64_t n_frame
                                   (hipStream_t)stream);
 }
 
+// The tree's scores (score_kernel.hip): the two entries above with the leaf's
+// entry of node_score written in place of its class.
+int vad_tree_predict_scores(const vad_tree_plan* t, const float* node_score, const float* x, int64_t n,
+                            float* scores, void* stream) {
+  if (!t || n < 0) return VAD_EINVAL;
+  if (n == 0) return VAD_OK;
+  if (!x || !scores || !node_score) return VAD_EINVAL;
+  if (n > INT64_MAX / 4 / t->n_features || overlap(x, (size_t)n * t->n_features * 4, scores, (size_t)n * 4))
+    return VAD_EINVAL;
+  return (int)launch_tree_row_scores(t->nodes_dev, t->n_nodes, node_score, x, n, t->n_features, scores,
+                                     (hipStream_t)stream);
+}
+
+int vad_features_tree_scores(const vad_tree_plan* t, const float* node_score, const float* mfcc, int64_t n_frames,
+                             int32_t mfcc_n, int32_t mode, float* scores, void* stream) {
+  if (!t || n_frames < 0 || mfcc_n <= 0 || mfcc_n > VAD_MAX_MFCC || (mode != 0 && mode != 1))
+    return VAD_EINVAL;
+  if (t->n_features > 3 * mfcc_n) return VAD_EINVAL;
+  const int64_t rows = n_frames > 5 ? n_frames - 5 : 0;
+  if (rows == 0) return VAD_OK;
+  if (!mfcc || !scores || !node_score) return VAD_EINVAL;
+  if (n_frames > INT64_MAX / 64 || overlap(mfcc, (size_t)n_frames * mfcc_n * 4, scores, (size_t)rows * 4))
+    return VAD_EINVAL;
+  return (int)launch_tree_window_scores(t->nodes_dev, t->cnodes_dev, t->n_nodes, node_score, mfcc, rows, mfcc_n,
+                                        mode, scores, (hipStream_t)stream);
+}
+
 int vad_simple_features(const float* frames, int64_t n_frames, int32_t frame_len,
                         int64_t frame_stride, int32_t fft_len, int32_t pad, int32_t band_bins,
                         int32_t n_bands, double* out, void* stream) {

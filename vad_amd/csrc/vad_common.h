@@ -233,6 +233,12 @@ hipError_t launch_tree_rows(const TreeNode* nodes, int n_nodes, const float* x, 
 hipError_t launch_tree_windows(const TreeNode* nodes, const TreeNodeC* cnodes, int n_nodes,
                                const float* mfcc, int64_t n_rows,
                                int mfcc_n, int mode, uint8_t* labels, hipStream_t st);
+// The same walks ending in node_score[leaf node] (score_kernel.hip).
+hipError_t launch_tree_row_scores(const TreeNode* nodes, int n_nodes, const float* node_score, const float* x,
+                                  int64_t n, int dim, float* scores, hipStream_t st);
+hipError_t launch_tree_window_scores(const TreeNode* nodes, const TreeNodeC* cnodes, int n_nodes,
+                                     const float* node_score, const float* mfcc, int64_t n_rows, int mfcc_n, int mode,
+                                     float* scores, hipStream_t st);
 // FFN training (train_kernel.hip).  ffn_train_lds_bytes: LDS of one
 // workgroup of the step kernel (train) or of the evaluation kernel; the C
 // entries refuse what does not fit in 160 KiB before they launch.

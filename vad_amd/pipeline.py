@@ -142,26 +142,76 @@ class VadPipeline:
             _lib.ptr(ws), 0 if ws is None else ws.numel(), _lib.stream_ptr(stream)), fn)
         return out
 
-    def segments(self, audio, max_gap=0, min_run=0, active=1, capacity=None, stream=None, rate=None):
+    def scores(self, audio, active=1, out=None, stream=None, rate=None):
+        """float32 (F-5,) speech scores of every window of a device clip
+        (float32 or int16): the classifier's estimate in [0, 1] that the window
+        is of class index ``active`` -- the softmax of the FFN's logits, or the
+        class fraction of the tree's leaf (vad_amd.scores).  The windows and
+        features are those of labels(); rate as there."""
+        from .scores import scores_from_logits
+        if self.ffn is None:
+            raise ValueError("pipeline has no classifier")
+        if not (isinstance(audio, torch.Tensor) and audio.is_cuda
+                and audio.dtype in (torch.float32, torch.int16) and audio.is_contiguous()):
+            raise TypeError("audio must be a contiguous float32 or int16 CUDA tensor")
+        audio = self._at_rate(audio, rate, stream)
+        mfcc = self.mfcc(audio, stream=stream)
+        if not isinstance(self.ffn, FFNClassifier):
+            return self.ffn.window_scores(mfcc, self.mode, active, out=out, stream=stream)
+        from .plan import window_logits
+        _, logits = window_logits(self.ffn.plan, mfcc, self.mode, stream=stream)
+        return scores_from_logits(logits, active, out=out, stream=stream)
+
+    def _decided(self, scores_or_labels, on, off, max_gap, min_run, pad, active, stream, batch=None):
+        """The operating-point chain: scores -> hysteresis(on, off) (or the
+        classifier's labels when on is None) -> close(max_gap) -> open(min_run)
+        -> padding; uint8 0 / 1 for the segment stage with active = 1."""
+        from . import scores as S
+        from . import segments as G
+        x = scores_or_labels
+        if batch is None:
+            lab = S.score_labels(x, on, off, stream=stream) if on is not None else x
+            lab = G.smooth_labels(lab, max_gap, min_run, active=1 if on is not None else active, stream=stream)
+            return S.dilate_labels(lab, pad, active=1, stream=stream)
+        lab = S.batch_score_labels(x, batch, on, off, stream=stream) if on is not None else x
+        lab = G.batch_smooth_labels(lab, batch, max_gap, min_run, active=1 if on is not None else active,
+                                    stream=stream)
+        return S.batch_dilate_labels(lab, batch, pad, active=1, stream=stream)
+
+    def segments(self, audio, max_gap=0, min_run=0, active=1, capacity=None, stream=None, rate=None,
+                 on=None, off=None, pad=(0, 0)):
         """Speech segments of a device clip: labels(), then
         vad_amd.segments.label_segments at the pipeline's framing (max_gap /
         min_run in windows).  Returns a Segments; no synchronisation.  With
-        ``rate`` the segments are in samples of the converted clip."""
+        ``rate`` the segments are in samples of the converted clip.
+        on / off / pad choose an operating point (vad_amd.scores): with ``on``
+        the labels are decided from scores() by hysteresis (speech from a
+        window with score >= on until one with score < off; off defaults to
+        on), smoothed by max_gap / min_run, and every run then grows by
+        pad = (before, after) windows.  Left at their defaults, the labels are
+        the classifier's and nothing else runs."""
         from .segments import label_segments
         audio = self._at_rate(audio, rate, stream)
+        if on is not None or tuple(pad) != (0, 0):
+            x = self.scores(audio, active, stream=stream) if on is not None else self.labels(audio, stream=stream)
+            lab = self._decided(x, on, off, max_gap, min_run, pad, active, stream)
+            return label_segments(lab, audio.numel(), self.cfg.frame_size, self.cfg.hop, active=1,
+                                  capacity=capacity, stream=stream)
         labels = self.labels(audio, stream=stream)
         return label_segments(labels, audio.numel(), self.cfg.frame_size, self.cfg.hop, max_gap=max_gap,
                               min_run=min_run, active=active, capacity=capacity, stream=stream)
 
-    def voiced(self, audio, max_gap=0, min_run=0, active=1, stream=None, rate=None):
+    def voiced(self, audio, max_gap=0, min_run=0, active=1, stream=None, rate=None, on=None, off=None, pad=(0, 0)):
         """The voiced samples of a device clip (float32 or int16, bits
         copied), packed in order: segments(), then the device gather.  The
         result is trimmed to the voiced count, which lives on the device, so
         this call synchronises once (vad_amd.segments.voiced_audio is the form
-        that does not).  With ``rate`` they are samples of the converted clip."""
+        that does not).  With ``rate`` they are samples of the converted clip.
+        on / off / pad: as segments()."""
         from .segments import voiced_audio
         audio = self._at_rate(audio, rate, stream)
-        seg = self.segments(audio, max_gap=max_gap, min_run=min_run, active=active, stream=stream)
+        seg = self.segments(audio, max_gap=max_gap, min_run=min_run, active=active, stream=stream, on=on, off=off,
+                            pad=pad)
         out, counts = voiced_audio(audio, seg, stream=stream)
         if stream is not None:
             stream.synchronize()
@@ -207,24 +257,43 @@ class VadPipeline:
         h = batch.host
         return [rows[f0:f0 + r] for f0, r in zip(h["frame0"].tolist(), h["n_rows"].tolist())]
 
-    def segments_batch(self, batch, max_gap=0, min_run=0, active=1, capacity=None, stream=None, rate=None):
+    def scores_batch(self, batch, active=1, stream=None, rate=None):
+        """The scores of every clip of a ClipBatch from ONE run of scores()
+        over the packed buffer: a BatchScores whose [k] is the view of clip
+        k's scores, equal to scores(clip k).  No synchronisation."""
+        from .scores import BatchScores
+        batch = self._batch_at_rate(batch, rate, stream)
+        self._check_batch(batch)
+        return BatchScores(self.scores(batch.data, active, stream=stream), batch)
+
+    def segments_batch(self, batch, max_gap=0, min_run=0, active=1, capacity=None, stream=None, rate=None,
+                       on=None, off=None, pad=(0, 0)):
         """Speech segments of every clip of a ClipBatch: labels_batch(), then
         vad_amd.segments.batch_label_segments.  Returns a BatchSegments; no
-        synchronisation."""
+        synchronisation.  on / off / pad: as segments(), every clip a sequence
+        of its own."""
         from .segments import batch_label_segments
         batch = self._batch_at_rate(batch, rate, stream)
+        if on is not None or tuple(pad) != (0, 0):
+            x = (self.scores_batch(batch, active, stream=stream).scores if on is not None
+                 else self.labels_batch(batch, stream=stream).labels)
+            lab = self._decided(x, on, off, max_gap, min_run, pad, active, stream, batch=batch)
+            return batch_label_segments(lab, batch, active=1, capacity=capacity, stream=stream)
         labels = self.labels_batch(batch, stream=stream)
         return batch_label_segments(labels, batch, max_gap=max_gap, min_run=min_run, active=active,
                                     capacity=capacity, stream=stream)
 
-    def voiced_batch(self, batch, max_gap=0, min_run=0, active=1, stream=None, rate=None):
+    def voiced_batch(self, batch, max_gap=0, min_run=0, active=1, stream=None, rate=None, on=None, off=None,
+                     pad=(0, 0)):
         """The voiced samples of every clip of a ClipBatch, packed clip after
         clip: ``(voiced, offsets)`` with clip k's samples
         voiced[offsets[k]:offsets[k + 1]] (offsets: (n_clips + 1,) int64
-        numpy).  Synchronises once, as voiced() does."""
+        numpy).  Synchronises once, as voiced() does.  on / off / pad: as
+        segments()."""
         from .segments import batch_voiced_audio
         batch = self._batch_at_rate(batch, rate, stream)
-        seg = self.segments_batch(batch, max_gap=max_gap, min_run=min_run, active=active, stream=stream)
+        seg = self.segments_batch(batch, max_gap=max_gap, min_run=min_run, active=active, stream=stream, on=on,
+                                  off=off, pad=pad)
         out, _ = batch_voiced_audio(batch, seg, stream=stream)
         if stream is not None:
             stream.synchronize()

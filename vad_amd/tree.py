@@ -24,6 +24,7 @@ from .plan import _out
 
 _KEYS = ("feature", "threshold", "left", "right", "leaf", "nan_left", "classes")
 _TRAIN_KEYS = ("n_node_samples", "depth", "value")  # optional: written by a trained tree only
+_PROBA_KEYS = ("proba",)  # optional: written by a tree converted from sklearn
 
 
 class TreePlan:
@@ -63,7 +64,7 @@ class TreeClassifier:
     """GPU decision tree with the sklearn ``predict`` protocol."""
 
     def __init__(self, feature, threshold, left, right, leaf, nan_left, classes, n_features,
-                 n_node_samples=None, depth=None, value=None):
+                 n_node_samples=None, depth=None, value=None, proba=None):
         self.nan_left = np.asarray(nan_left, np.uint8)
         self.feature = np.asarray(feature, np.int32)
         self.threshold = np.asarray(threshold, np.float64)
@@ -77,6 +78,9 @@ class TreeClassifier:
         self.n_node_samples = None if n_node_samples is None else np.asarray(n_node_samples, np.int32)
         self.depth = None if depth is None else np.asarray(depth, np.int32)
         self.value = None if value is None else np.asarray(value, np.int32)
+        # sklearn's tree_.value per node, (n_nodes, n_classes) float64 (from_sklearn; None
+        # otherwise): class fractions or weighted counts, what predict_proba normalises
+        self.proba = None if proba is None else np.asarray(proba, np.float64)
         self._plan = None
 
     # -- construction ----------------------------------------------------
@@ -93,7 +97,7 @@ class TreeClassifier:
         feature = np.where(np.asarray(t.children_left) < 0, -1, np.asarray(t.feature))
         nan_left = np.asarray(getattr(t, "missing_go_to_left", np.zeros(t.node_count, np.uint8)))
         return cls(feature, t.threshold, t.children_left, t.children_right, leaf, nan_left,
-                   clf.classes_, t.n_features)
+                   clf.classes_, t.n_features, proba=value)
 
     @staticmethod
     def looks_like_sklearn_tree(obj):
@@ -104,14 +108,14 @@ class TreeClassifier:
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
-            extra = {k: z[k] for k in _TRAIN_KEYS if k in z.files}
+            extra = {k: z[k] for k in _TRAIN_KEYS + _PROBA_KEYS if k in z.files}
             return cls(*(z[k] for k in _KEYS), int(z["n_features"]), **extra)
 
     def save(self, path):
         np.savez(path, feature=self.feature, threshold=self.threshold, left=self.left,
                  right=self.right, leaf=self.leaf, nan_left=self.nan_left, classes=self.classes_,
                  n_features=np.int64(self.n_features),
-                 **{k: getattr(self, k) for k in _TRAIN_KEYS if getattr(self, k) is not None})
+                 **{k: getattr(self, k) for k in _TRAIN_KEYS + _PROBA_KEYS if getattr(self, k) is not None})
 
     @property
     def plan(self) -> TreePlan:
@@ -123,6 +127,32 @@ class TreeClassifier:
     @property
     def in_dim(self):
         return self.n_features
+
+    # -- scores ------------------------------------------------------------
+    def score_table(self, active=1):
+        """float32 (n_nodes,): the share of class index ``active`` among a
+        node's training rows, by sklearn's predict_proba formula in float64
+        (value / value.sum(), a zero sum taken as 1) rounded once to float32.
+        From ``proba`` (a tree converted from sklearn) or the integer class
+        counts ``value`` (a tree trained here); ValueError with neither."""
+        v = self.proba if self.proba is not None else self.value
+        if v is None:
+            raise ValueError("the tree has neither sklearn's node values (proba) nor class counts (value): "
+                             "convert it again with from_sklearn, or train it with vad_amd.tree_train")
+        v = np.asarray(v, np.float64)
+        if v.ndim != 2 or v.shape[0] != self.feature.shape[0]:
+            raise ValueError("node values must be (n_nodes, n_classes)")
+        if not 0 <= int(active) < v.shape[1]:
+            raise ValueError(f"active must be a class index below {v.shape[1]}, got {active}")
+        norm = v.sum(axis=1)
+        norm[norm == 0.0] = 1.0
+        return np.ascontiguousarray((v[:, int(active)] / norm).astype(np.float32))
+
+    def window_scores(self, mfcc, mode=_lib.FEAT_ANALYSER, active=1, out=None, stream=None):
+        """Scores (float32, device) of every 5-frame window of an MFCC sequence
+        (vad_amd.scores.tree_window_scores)."""
+        from .scores import tree_window_scores
+        return tree_window_scores(self, mfcc, mode, active, out=out, stream=stream)
 
     # -- inference --------------------------------------------------------
     def predict_device(self, x, out=None, stream=None):
