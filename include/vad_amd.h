@@ -627,6 +627,49 @@ int vad_stream_step_tree(const vad_mfcc_plan* plan, const vad_tree_plan* tree, c
                          uint8_t* labels, float* mfcc_scratch, void* stream);
 /* largest table the hop kernel walks from LDS; -1 on a bad plan */
 int64_t vad_stream_tree_max_lds_nodes(const vad_mfcc_plan* plan);
+
+/* Scored hops: the operating point on the live path.  Each entry is the label
+ * entry of the same name plus `active`, `scores` and `score_block_stride`:
+ * besides labels[k * label_block_stride + s] the hop kernel writes the fp32
+ * score of class index `active`, in [0, 1], to
+ * scores[k * score_block_stride + s] -- NaN for a hop whose stream has no
+ * window yet (label 255).  Labels, frames, ring and count are those of the
+ * label entry, bit for bit.
+ *   FFN   s = 1 / (1 + sum_{j != active} expf(z_j - z_active)) of the window's
+ *         logits, 0 when a logit is inf or NaN: vad_scores_from_logits' function
+ *         (one device function serves both).
+ *   tree  the plan's score table (vad_tree_plan_set_scores: a host array of
+ *         n_classes rows of n_nodes floats, row c the score of class c per
+ *         node, copied to the device; it may be set again) read at the leaf
+ *         NODE the walk ends in, row `active`: vad_features_tree_scores' value.
+ * Refusals: those of the label entries, plus VAD_EINVAL for `active` outside
+ * [0, the classifier's classes) (the FFN's outputs; the rows of the tree's
+ * score table), a tree plan without a score table, a null `scores` and, for
+ * n_hops > 1, score_block_stride < n_streams.  All before any device call. */
+int vad_tree_plan_set_scores(vad_tree_plan* plan, const float* table /* host, n_classes x n_nodes */,
+                             int32_t n_classes);
+int32_t vad_tree_plan_score_classes(const vad_tree_plan* plan); /* 0: no table; -1: null plan */
+int vad_stream_hops_scores(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
+                           int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len,
+                           int64_t n_streams, int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count,
+                           uint8_t* labels, int64_t label_block_stride, int32_t active, float* scores,
+                           int64_t score_block_stride, void* stream);
+int vad_stream_hops_scores_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames,
+                               int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                               int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                               float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                               int32_t active, float* scores, int64_t score_block_stride, void* stream);
+int vad_stream_hops_tree_scores(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                                int64_t frame_stride, int32_t frame_len, const float* hop, int64_t hop_stride,
+                                int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride, int32_t walk,
+                                int32_t active, float* scores, int64_t score_block_stride, void* stream);
+int vad_stream_hops_tree_scores_i16(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                                    int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                                    int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                    float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                                    int32_t walk, int32_t active, float* scores, int64_t score_block_stride,
+                                    void* stream);
 /* Replay a captured hipGraph (hipGraphExec_t) on `stream`: the per-hop step
  * of a StreamBatch captured with its host I/O (the H2D copy of every
  * stream's new samples from pinned memory, the hop kernel, the D2H copy of
@@ -975,6 +1018,70 @@ int vad_stream_segments_flush_i16(int64_t n_streams, int64_t max_gap, int64_t mi
                                   int32_t hop, void* state, int64_t* segments, int64_t capacity, int64_t* found,
                                   int16_t* history, int64_t history_elems, int16_t* voiced, int32_t* voiced_len,
                                   void* stream);
+
+/* The operating point in the streaming segmenter: the clip chain of "Speech
+ * scores" (hysteresis -> smooth -> dilate -> segments) one window at a time.
+ * `block` is the (n_hops, n_streams) block the hop kernels wrote, row stride
+ * block_stride elements: fp32 scores (block_is_scores 1) or uint8 labels (0).
+ *   hysteresis  scores only: h = 1 at s >= on, 0 at s < off or NaN, else the
+ *               previous h (0 before a stream's first window); the window is
+ *               active iff h.  `active` is not read.  Labels: active iff
+ *               label == active, as vad_stream_segments.
+ *   padding     a run [r0, r1] that survives close(max_gap) and open(min_run)
+ *               becomes [max(r0 - pad_before, 0), min(r1 + pad_after, N - 1)],
+ *               N the stream's window count (known at the flush), before the
+ *               close(frame_size / hop - 1) join: vad_label_dilate's result.
+ *   delay       D = vad_stream_seg_delay_pad = vad_stream_seg_delay +
+ *               pad_before; pad_after adds none.  The flush row count and the
+ *               history grow with D (the _pad sizing entries; each equals the
+ *               entry without _pad at pads (0, 0)).
+ * After the flush a stream's rows and voiced samples are vad_label_segments /
+ * vad_gather_segments of vad_label_dilate(vad_label_smooth(vad_score_labels(
+ * scores))) on its equivalent clip, bit for bit.  State, history, segments,
+ * found and the voiced rows are those of vad_stream_segments*; the state's
+ * size does not change and all-zero is still a stream before its first hop.
+ * One kernel, no LDS, no atomics, no workgroup waits on another.
+ * Refusals: those of vad_stream_segments*, plus VAD_EINVAL for on / off outside
+ * [0, 1], off > on or a NaN threshold, a negative pad (or one above 2^29), a
+ * block_is_scores other than 0 / 1, a score block that is not 4-byte aligned,
+ * and a history that would pass 2^30 elements per stream.  The flush forms
+ * take and check the same operating point. */
+int64_t vad_stream_seg_delay_pad(int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                                 int64_t pad_before, int64_t pad_after);
+int64_t vad_stream_seg_flush_rows_pad(int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                                      int64_t pad_before, int64_t pad_after);
+int64_t vad_stream_seg_history_elems_pad(int64_t n_streams, int32_t n_hops_max, int64_t max_gap, int64_t min_run,
+                                         int32_t frame_size, int32_t hop, int64_t pad_before, int64_t pad_after);
+int vad_stream_segments_op(const void* block, int32_t block_is_scores, int64_t block_stride, int64_t n_streams,
+                           int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size,
+                           int32_t hop, float on, float off, int64_t pad_before, int64_t pad_after, void* state,
+                           int64_t* segments, int64_t capacity, int64_t* found, void* stream);
+int vad_stream_segments_op_f32(const void* block, int32_t block_is_scores, int64_t block_stride, int64_t n_streams,
+                               int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size,
+                               int32_t hop, float on, float off, int64_t pad_before, int64_t pad_after, void* state,
+                               int64_t* segments, int64_t capacity, int64_t* found, const float* hop_samples,
+                               int64_t hop_stride, int64_t hop_block_stride, float* history, int64_t history_elems,
+                               float* voiced, int32_t* voiced_len, void* stream);
+int vad_stream_segments_op_i16(const void* block, int32_t block_is_scores, int64_t block_stride, int64_t n_streams,
+                               int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size,
+                               int32_t hop, float on, float off, int64_t pad_before, int64_t pad_after, void* state,
+                               int64_t* segments, int64_t capacity, int64_t* found, const int16_t* hop_samples,
+                               int64_t hop_stride, int64_t hop_block_stride, int16_t* history, int64_t history_elems,
+                               int16_t* voiced, int32_t* voiced_len, void* stream);
+int vad_stream_segments_op_flush(int64_t n_streams, int32_t block_is_scores, int64_t max_gap, int64_t min_run,
+                                 int32_t frame_size, int32_t hop, float on, float off, int64_t pad_before,
+                                 int64_t pad_after, void* state, int64_t* segments, int64_t capacity, int64_t* found,
+                                 void* stream);
+int vad_stream_segments_op_flush_f32(int64_t n_streams, int32_t block_is_scores, int64_t max_gap, int64_t min_run,
+                                     int32_t frame_size, int32_t hop, float on, float off, int64_t pad_before,
+                                     int64_t pad_after, void* state, int64_t* segments, int64_t capacity,
+                                     int64_t* found, float* history, int64_t history_elems, float* voiced,
+                                     int32_t* voiced_len, void* stream);
+int vad_stream_segments_op_flush_i16(int64_t n_streams, int32_t block_is_scores, int64_t max_gap, int64_t min_run,
+                                     int32_t frame_size, int32_t hop, float on, float off, int64_t pad_before,
+                                     int64_t pad_after, void* state, int64_t* segments, int64_t capacity,
+                                     int64_t* found, int16_t* history, int64_t history_elems, int16_t* voiced,
+                                     int32_t* voiced_len, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Resampling: audio at another rate to the front end's (the mel bank, the

@@ -119,6 +119,14 @@ SIGNATURES = {
     "vad_stream_step_tree": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp,
                                      c_vp]),
     "vad_stream_tree_max_lds_nodes": (c_i64, [c_vp]),
+    "vad_tree_plan_set_scores": (c_int, [c_vp, c_vp, c_i32]),
+    "vad_tree_plan_score_classes": (c_i32, [c_vp]),
+    **{"vad_stream_hops_scores" + t: (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32, c_i64,
+                                              c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp])
+       for t in ("", "_i16")},
+    **{"vad_stream_hops_tree_scores" + t: (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32,
+                                                   c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp])
+       for t in ("", "_i16")},
     "vad_graph_launch": (c_int, [c_vp, c_vp]),
     "vad_graph_plan_create": (c_int, [c_vp, c_vp, c_vp]),
     "vad_graph_plan_launch": (c_int, [c_vp, c_vp]),
@@ -169,6 +177,21 @@ SIGNATURES = {
                                               c_i64, c_vp, c_vp, c_vp]),
     "vad_stream_segments_flush_i16": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp,
                                               c_i64, c_vp, c_vp, c_vp]),
+    "vad_stream_seg_delay_pad": (c_i64, [c_i64, c_i64, c_i32, c_i32, c_i64, c_i64]),
+    "vad_stream_seg_flush_rows_pad": (c_i64, [c_i64, c_i64, c_i32, c_i32, c_i64, c_i64]),
+    "vad_stream_seg_history_elems_pad": (c_i64, [c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_i64, c_i64]),
+    # block, is_scores, stride, S, n_hops, active, max_gap, min_run, L, H, on, off, pad_before, pad_after, tables
+    "vad_stream_segments_op": (c_int, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32, c_f32,
+                                       c_f32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    **{"vad_stream_segments_op_" + t: (c_int, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32,
+                                               c_f32, c_f32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64,
+                                               c_i64, c_vp, c_i64, c_vp, c_vp, c_vp])
+       for t in ("f32", "i16")},
+    "vad_stream_segments_op_flush": (c_int, [c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_f32, c_f32, c_i64, c_i64,
+                                             c_vp, c_vp, c_i64, c_vp, c_vp]),
+    **{"vad_stream_segments_op_flush_" + t: (c_int, [c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_f32, c_f32, c_i64,
+                                                     c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp])
+       for t in ("f32", "i16")},
     "vad_resample_tile_outputs": (c_i32, []),
     "vad_resample_plan_create": (c_int, [c_i32, c_i32, c_vp, c_i32, c_vp]),
     "vad_resample_plan_upload": (c_int, [c_vp]),

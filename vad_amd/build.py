@@ -57,7 +57,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    deps = sources() + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]  # .inc: kernel bodies included per kernel
     deps.append(os.path.join(os.path.dirname(HERE), "include", "vad_amd.h"))
     return any(os.path.getmtime(d) > t for d in deps)
 

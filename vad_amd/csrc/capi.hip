@@ -647,6 +647,8 @@ struct vad_tree_plan {
   TreeNodeC* cnodes_dev;  // compact copy for the LDS-resident window walk
   int n_nodes;
   int n_features;
+  float* score_dev;      // (n_score_classes, n_nodes) node scores, or null (vad_tree_plan_set_scores)
+  int n_score_classes;
 };
 
 int vad_tree_plan_create(int32_t n_nodes, const int32_t* feature, const double* threshold,
@@ -709,9 +711,31 @@ int vad_tree_plan_destroy(vad_tree_plan* p) {
   if (!p) return VAD_OK;
   (void)hipFree(p->nodes_dev);
   (void)hipFree(p->cnodes_dev);
+  if (p->score_dev) (void)hipFree(p->score_dev);
   free(p);
   return VAD_OK;
 }
+
+// The plan's score table: row c holds, per node, the score of class index c
+// (TreeClassifier.score_table(c)); the scored hop entries read row `active`.
+int vad_tree_plan_set_scores(vad_tree_plan* p, const float* table, int32_t n_classes) {
+  if (!p || !table || n_classes <= 0 || n_classes > 255) return VAD_EINVAL;
+  float* dev = nullptr;
+  const size_t bytes = (size_t)n_classes * (size_t)p->n_nodes * sizeof(float);
+  hipError_t e = hipMalloc((void**)&dev, bytes);
+  if (e != hipSuccess) return (int)e;
+  e = hipMemcpy(dev, table, bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(dev);
+    return (int)e;
+  }
+  if (p->score_dev) (void)hipFree(p->score_dev);  // hipFree waits for the kernels that read it
+  p->score_dev = dev;
+  p->n_score_classes = n_classes;
+  return VAD_OK;
+}
+
+int32_t vad_tree_plan_score_classes(const vad_tree_plan* p) { return p ? p->n_score_classes : -1; }
 
 int vad_tree_predict(const vad_tree_plan* t, const float* x, int64_t n, uint8_t* labels,
                      void* stream) {
@@ -1156,11 +1180,14 @@ static int stream_hops_entry(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn,
                              int64_t frame_stride, int32_t frame_len, const void* hop, int hop_bytes,
                              int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,
                              int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels,
-                             int64_t label_block_stride, void* stream) {
+                             int64_t label_block_stride, void* stream, bool scored = false, int32_t active = 0,
+                             float* scores = nullptr, int64_t score_block_stride = 0) {
   if (!plan || !ffn || n_streams < 0 || n_hops < 0 || frame_len <= 0 || frame_len > 1024 || hop_len <= 0 ||
       hop_len > frame_len || frame_stride < frame_len || hop_stride < hop_len)
     return VAD_EINVAL;
   if (n_hops > 1 && label_block_stride < n_streams) return VAD_EINVAL;  // label rows of two hops would overlap
+  if (scored && (active < 0 || active >= ffn->net.n_classes)) return VAD_EINVAL;
+  if (scored && n_hops > 1 && score_block_stride < n_streams) return VAD_EINVAL;  // score rows likewise
   // hop k's block must not be hop k-1's (a zero or negative stride would
   // replay, or walk backwards over, the new samples), and no two (hop,
   // stream) rows may overlap: either ordering of a disjoint layout is fine,
@@ -1169,10 +1196,16 @@ static int stream_hops_entry(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn,
   if (n_hops > 1 && !vad_hop_layout_disjoint(n_streams, n_hops, hop_block_stride, hop_stride, hop_len))
     return VAD_EINVAL;
   if (n_streams == 0 || n_hops == 0) return VAD_OK;
-  if (!frames || !hop || !ring || !count || !labels) return VAD_EINVAL;
+  if (!frames || !hop || !ring || !count || !labels || (scored && !scores)) return VAD_EINVAL;
   if (ffn->net.dims[0] > 3 * plan->host.mfcc_n) return VAD_EINVAL;
   if (plan->generic()) return VAD_EUNSUPPORTED;  // its FFT is the 256-point Stockham of fft_n = 512
   if (plan->spec == kSpecWindow) return VAD_EUNSUPPORTED;  // its table blob carries no analysis window
+  if (scored)
+    return (int)launch_stream_hop_scores(plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps,
+                                         ffn->net, frames, frame_stride, frame_len, hop, hop_bytes, hop_stride,
+                                         hop_len, n_streams, plan->host.mfcc_n, ring, count, labels, n_hops,
+                                         hop_block_stride, label_block_stride, active, scores, score_block_stride,
+                                         (hipStream_t)stream);
   return (int)launch_stream_hop(plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps, ffn->net,
                                 frames, frame_stride, frame_len, hop, hop_bytes, hop_stride, hop_len, n_streams,
                                 plan->host.mfcc_n, ring, count, labels, n_hops, hop_block_stride,
@@ -1193,6 +1226,28 @@ int vad_stream_hops_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, floa
                         uint8_t* labels, int64_t label_block_stride, void* stream) {
   return stream_hops_entry(plan, ffn, frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len, n_streams,
                            n_hops, hop_block_stride, ring, count, labels, label_block_stride, stream);
+}
+
+// The scored forms: the label entries plus one fp32 score of class `active`
+// per (hop, stream), scores[k * score_block_stride + s].
+int vad_stream_hops_scores(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
+                           int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len,
+                           int64_t n_streams, int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count,
+                           uint8_t* labels, int64_t label_block_stride, int32_t active, float* scores,
+                           int64_t score_block_stride, void* stream) {
+  return stream_hops_entry(plan, ffn, frames, frame_stride, frame_len, hop, 4, hop_stride, hop_len, n_streams,
+                           n_hops, hop_block_stride, ring, count, labels, label_block_stride, stream, true, active,
+                           scores, score_block_stride);
+}
+
+int vad_stream_hops_scores_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames,
+                               int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                               int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                               float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                               int32_t active, float* scores, int64_t score_block_stride, void* stream) {
+  return stream_hops_entry(plan, ffn, frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len, n_streams,
+                           n_hops, hop_block_stride, ring, count, labels, label_block_stride, stream, true, active,
+                           scores, score_block_stride);
 }
 
 int vad_stream_hop(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
@@ -1239,19 +1294,29 @@ static int stream_hops_tree_entry(const vad_mfcc_plan* plan, const vad_tree_plan
                                   int64_t frame_stride, int32_t frame_len, const void* hop, int hop_bytes,
                                   int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,
                                   int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels,
-                                  int64_t label_block_stride, int32_t walk, void* stream) {
+                                  int64_t label_block_stride, int32_t walk, void* stream, bool scored = false,
+                                  int32_t active = 0, float* scores = nullptr, int64_t score_block_stride = 0) {
   if (!plan || !tree || n_streams < 0 || n_hops < 0 || frame_len <= 0 || frame_len > 1024 || hop_len <= 0 ||
       hop_len > frame_len || frame_stride < frame_len || hop_stride < hop_len)
     return VAD_EINVAL;
   if (walk != VAD_TREE_WALK_AUTO && walk != VAD_TREE_WALK_GLOBAL) return VAD_EINVAL;
   if (n_hops > 1 && label_block_stride < n_streams) return VAD_EINVAL;  // label rows of two hops would overlap
+  if (scored && !tree->score_dev) return VAD_EINVAL;  // vad_tree_plan_set_scores first
+  if (scored && (active < 0 || active >= tree->n_score_classes)) return VAD_EINVAL;
+  if (scored && n_hops > 1 && score_block_stride < n_streams) return VAD_EINVAL;
   if (n_hops > 1 && !vad_hop_layout_disjoint(n_streams, n_hops, hop_block_stride, hop_stride, hop_len))
     return VAD_EINVAL;
   if (n_streams == 0 || n_hops == 0) return VAD_OK;
-  if (!frames || !hop || !ring || !count || !labels) return VAD_EINVAL;
+  if (!frames || !hop || !ring || !count || !labels || (scored && !scores)) return VAD_EINVAL;
   if (tree->n_features > 3 * plan->host.mfcc_n) return VAD_EINVAL;
   if (plan->generic()) return VAD_EUNSUPPORTED;  // its FFT is the 256-point Stockham of fft_n = 512
   if (plan->spec == kSpecWindow) return VAD_EUNSUPPORTED;  // its table blob carries no analysis window
+  if (scored)
+    return (int)launch_stream_hop_tree_scores(
+        plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps, tree->cnodes_dev, tree->nodes_dev,
+        tree->n_nodes, walk == VAD_TREE_WALK_GLOBAL, frames, frame_stride, frame_len, hop, hop_bytes, hop_stride,
+        hop_len, n_streams, plan->host.mfcc_n, ring, count, labels, n_hops, hop_block_stride, label_block_stride,
+        tree->score_dev + (size_t)active * (size_t)tree->n_nodes, scores, score_block_stride, (hipStream_t)stream);
   return (int)launch_stream_hop_tree(plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps,
                                      tree->cnodes_dev, tree->nodes_dev, tree->n_nodes, walk == VAD_TREE_WALK_GLOBAL,
                                      frames, frame_stride, frame_len, hop, hop_bytes, hop_stride, hop_len, n_streams,
@@ -1273,6 +1338,27 @@ int vad_stream_hops_tree_i16(const vad_mfcc_plan* plan, const vad_tree_plan* tre
                              int32_t* count, uint8_t* labels, int64_t label_block_stride, int32_t walk, void* stream) {
   return stream_hops_tree_entry(plan, tree, frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len, n_streams,
                                 n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk, stream);
+}
+
+int vad_stream_hops_tree_scores(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                                int64_t frame_stride, int32_t frame_len, const float* hop, int64_t hop_stride,
+                                int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride, int32_t walk,
+                                int32_t active, float* scores, int64_t score_block_stride, void* stream) {
+  return stream_hops_tree_entry(plan, tree, frames, frame_stride, frame_len, hop, 4, hop_stride, hop_len, n_streams,
+                                n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk, stream, true,
+                                active, scores, score_block_stride);
+}
+
+int vad_stream_hops_tree_scores_i16(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                                    int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                                    int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                    float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                                    int32_t walk, int32_t active, float* scores, int64_t score_block_stride,
+                                    void* stream) {
+  return stream_hops_tree_entry(plan, tree, frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len, n_streams,
+                                n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk, stream, true,
+                                active, scores, score_block_stride);
 }
 
 int vad_stream_step_tree(const vad_mfcc_plan* plan, const vad_tree_plan* tree, const float* frames,
@@ -1309,13 +1395,32 @@ int64_t vad_stream_seg_flush_rows(int64_t max_gap, int64_t min_run, int32_t fram
   return d < 0 ? -1 : d + 2 + (frame_size + hop - 1) / hop;
 }
 
+// The operating-point forms (vad_stream_segments_op*): pad_before more windows
+// of delay, pad_after none (stream_segments_kernel.hip's header).
+static bool seg_pad_ok(int64_t pad_before, int64_t pad_after) {
+  return pad_before >= 0 && pad_after >= 0 && pad_before <= kSegParamMax && pad_after <= kSegParamMax;
+}
+
+int64_t vad_stream_seg_delay_pad(int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                                 int64_t pad_before, int64_t pad_after) {
+  const int64_t d = vad_stream_seg_delay(max_gap, min_run, frame_size, hop);
+  return d < 0 || !seg_pad_ok(pad_before, pad_after) ? -1 : d + pad_before;
+}
+
+int64_t vad_stream_seg_flush_rows_pad(int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                                      int64_t pad_before, int64_t pad_after) {
+  const int64_t d = vad_stream_seg_delay_pad(max_gap, min_run, frame_size, hop, pad_before, pad_after);
+  return d < 0 ? -1 : d + 2 + (frame_size + hop - 1) / hop;
+}
+
 size_t vad_stream_seg_state_bytes(int64_t n_streams) {
   return n_streams > 0 ? (size_t)n_streams * kSegStreamStateBytes : 0;
 }
 
 // history elements one stream needs for blocks of n_hops hops (-1: bad arguments or past kSegRingMax)
-static int64_t seg_ring_need(int64_t n_hops, int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop) {
-  const int64_t d = vad_stream_seg_delay(max_gap, min_run, frame_size, hop);
+static int64_t seg_ring_need(int64_t n_hops, int64_t max_gap, int64_t min_run, int32_t frame_size, int32_t hop,
+                             int64_t pad_before = 0, int64_t pad_after = 0) {
+  const int64_t d = vad_stream_seg_delay_pad(max_gap, min_run, frame_size, hop, pad_before, pad_after);
   if (d < 0 || n_hops < 0) return -1;
   const int64_t need = (d + 3 + n_hops) * hop + frame_size;
   return need > kSegRingMax ? -1 : need;
@@ -1328,6 +1433,20 @@ int64_t vad_stream_seg_history_elems(int64_t n_streams, int32_t n_hops_max, int6
   return n_streams * need;
 }
 
+int64_t vad_stream_seg_history_elems_pad(int64_t n_streams, int32_t n_hops_max, int64_t max_gap, int64_t min_run,
+                                         int32_t frame_size, int32_t hop, int64_t pad_before, int64_t pad_after) {
+  const int64_t need = seg_ring_need(n_hops_max, max_gap, min_run, frame_size, hop, pad_before, pad_after);
+  if (need < 0 || n_streams < 0 || n_streams > INT32_MAX) return -1;
+  return n_streams * need;
+}
+
+// The operating point of the _op entries; null for the label entries.
+struct SegOpHost {
+  int32_t block_is_scores;
+  float on, off;
+  int64_t pad_before, pad_after;
+};
+
 // One body for the six entries: labels == NULL with flush set is a flush of
 // vad_stream_seg_flush_rows hops; audio_bytes 0 is the events-only form.
 // Every check comes before any HIP call, in the same order for every form.
@@ -1336,9 +1455,14 @@ static int stream_segments_entry(bool flush, const uint8_t* labels, int64_t labe
                                  int32_t frame_size, int32_t hop, void* state, int64_t* segments, int64_t capacity,
                                  int64_t* found, int audio_bytes, const void* hop_samples, int64_t hop_stride,
                                  int64_t hop_block_stride, void* history, int64_t history_elems, void* voiced,
-                                 int32_t* voiced_len, void* stream) {
-  const int64_t delay = vad_stream_seg_delay(max_gap, min_run, frame_size, hop);
-  if (delay < 0) return VAD_EINVAL;  // hop outside (0, frame_size], a negative gap or run
+                                 int32_t* voiced_len, void* stream, const SegOpHost* op = nullptr) {
+  const int64_t delay = op ? vad_stream_seg_delay_pad(max_gap, min_run, frame_size, hop, op->pad_before, op->pad_after)
+                           : vad_stream_seg_delay(max_gap, min_run, frame_size, hop);
+  if (delay < 0) return VAD_EINVAL;  // hop outside (0, frame_size], a negative gap, run or pad
+  if (op) {
+    if (op->block_is_scores != 0 && op->block_is_scores != 1) return VAD_EINVAL;
+    if (!(op->off >= 0.f && op->off <= op->on && op->on <= 1.f)) return VAD_EINVAL;  // NaN fails too
+  }
   if (n_streams < 0 || n_streams > INT32_MAX || n_hops < 0 || n_hops > INT32_MAX || capacity < 0)
     return VAD_EINVAL;
   if (active < 0 || active >= 255) return VAD_EINVAL;  // 255 is "no label yet"
@@ -1361,7 +1485,8 @@ static int stream_segments_entry(bool flush, const uint8_t* labels, int64_t labe
     if (reinterpret_cast<uintptr_t>(hop_samples) % audio_bytes || reinterpret_cast<uintptr_t>(history) % audio_bytes ||
         reinterpret_cast<uintptr_t>(voiced) % audio_bytes || reinterpret_cast<uintptr_t>(voiced_len) % 4)
       return VAD_EINVAL;
-    const int64_t need = seg_ring_need(flush ? 0 : n_hops, max_gap, min_run, frame_size, hop);
+    const int64_t need = seg_ring_need(flush ? 0 : n_hops, max_gap, min_run, frame_size, hop,
+                                       op ? op->pad_before : 0, op ? op->pad_after : 0);
     const int64_t ring = history_elems / n_streams;
     if (need < 0 || ring < need || ring > kSegRingMax) return VAD_EINVAL;
     a.hop_samples = hop_samples, a.hstride = hop_stride, a.hop_kstride = hop_block_stride;
@@ -1372,6 +1497,13 @@ static int stream_segments_entry(bool flush, const uint8_t* labels, int64_t labe
   a.max_gap = max_gap, a.min_run = min_run, a.join = frame_size / hop - 1, a.delay = delay;
   a.frame_size = frame_size, a.hop = hop;
   a.state = state, a.segments = segments, a.capacity = capacity, a.found = found;
+  if (op) {
+    if (!flush && op->block_is_scores && reinterpret_cast<uintptr_t>(labels) % 4) return VAD_EINVAL;
+    SegOpArgs o{};
+    o.on = op->on, o.off = op->off, o.is_scores = op->block_is_scores;
+    o.pad_before = op->pad_before, o.pad_after = op->pad_after;
+    return (int)launch_stream_segments_op(a, o, audio_bytes, (hipStream_t)stream);
+  }
   return (int)launch_stream_segments(a, audio_bytes, (hipStream_t)stream);
 }
 
@@ -1428,6 +1560,83 @@ int vad_stream_segments_flush_i16(int64_t n_streams, int64_t max_gap, int64_t mi
                                1, max_gap, min_run, frame_size, hop, state, segments, capacity, found, 2, nullptr,
                                0, 0, history, history_elems, voiced, voiced_len, stream);
 }
+
+// The operating-point forms: `block` holds fp32 scores (block_is_scores 1: the
+// hysteresis on / off decides; `active` is not read) or uint8 labels (0), and
+// a confirmed run is padded by pad_before / pad_after windows.
+#define VAD_SEG_OP_HOST const SegOpHost oph{block_is_scores, on, off, pad_before, pad_after}
+
+int vad_stream_segments_op(const void* block, int32_t block_is_scores, int64_t block_stride, int64_t n_streams,
+                           int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size,
+                           int32_t hop, float on, float off, int64_t pad_before, int64_t pad_after, void* state,
+                           int64_t* segments, int64_t capacity, int64_t* found, void* stream) {
+  VAD_SEG_OP_HOST;
+  return stream_segments_entry(false, (const uint8_t*)block, block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 0, nullptr, 0, 0, nullptr, 0,
+                               nullptr, nullptr, stream, &oph);
+}
+
+int vad_stream_segments_op_f32(const void* block, int32_t block_is_scores, int64_t block_stride, int64_t n_streams,
+                               int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size,
+                               int32_t hop, float on, float off, int64_t pad_before, int64_t pad_after, void* state,
+                               int64_t* segments, int64_t capacity, int64_t* found, const float* hop_samples,
+                               int64_t hop_stride, int64_t hop_block_stride, float* history, int64_t history_elems,
+                               float* voiced, int32_t* voiced_len, void* stream) {
+  VAD_SEG_OP_HOST;
+  return stream_segments_entry(false, (const uint8_t*)block, block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 4, hop_samples, hop_stride,
+                               hop_block_stride, history, history_elems, voiced, voiced_len, stream, &oph);
+}
+
+int vad_stream_segments_op_i16(const void* block, int32_t block_is_scores, int64_t block_stride, int64_t n_streams,
+                               int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run, int32_t frame_size,
+                               int32_t hop, float on, float off, int64_t pad_before, int64_t pad_after, void* state,
+                               int64_t* segments, int64_t capacity, int64_t* found, const int16_t* hop_samples,
+                               int64_t hop_stride, int64_t hop_block_stride, int16_t* history, int64_t history_elems,
+                               int16_t* voiced, int32_t* voiced_len, void* stream) {
+  VAD_SEG_OP_HOST;
+  return stream_segments_entry(false, (const uint8_t*)block, block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 2, hop_samples, hop_stride,
+                               hop_block_stride, history, history_elems, voiced, voiced_len, stream, &oph);
+}
+
+// Flush: the thresholds are not read (every flush window is inactive), but
+// they are checked like a push's, so one set of arguments serves both.
+int vad_stream_segments_op_flush(int64_t n_streams, int32_t block_is_scores, int64_t max_gap, int64_t min_run,
+                                 int32_t frame_size, int32_t hop, float on, float off, int64_t pad_before,
+                                 int64_t pad_after, void* state, int64_t* segments, int64_t capacity, int64_t* found,
+                                 void* stream) {
+  VAD_SEG_OP_HOST;
+  return stream_segments_entry(true, nullptr, 0, n_streams,
+                               vad_stream_seg_flush_rows_pad(max_gap, min_run, frame_size, hop, pad_before, pad_after),
+                               1, max_gap, min_run, frame_size, hop, state, segments, capacity, found, 0, nullptr, 0,
+                               0, nullptr, 0, nullptr, nullptr, stream, &oph);
+}
+
+int vad_stream_segments_op_flush_f32(int64_t n_streams, int32_t block_is_scores, int64_t max_gap, int64_t min_run,
+                                     int32_t frame_size, int32_t hop, float on, float off, int64_t pad_before,
+                                     int64_t pad_after, void* state, int64_t* segments, int64_t capacity,
+                                     int64_t* found, float* history, int64_t history_elems, float* voiced,
+                                     int32_t* voiced_len, void* stream) {
+  VAD_SEG_OP_HOST;
+  return stream_segments_entry(true, nullptr, 0, n_streams,
+                               vad_stream_seg_flush_rows_pad(max_gap, min_run, frame_size, hop, pad_before, pad_after),
+                               1, max_gap, min_run, frame_size, hop, state, segments, capacity, found, 4, nullptr, 0,
+                               0, history, history_elems, voiced, voiced_len, stream, &oph);
+}
+
+int vad_stream_segments_op_flush_i16(int64_t n_streams, int32_t block_is_scores, int64_t max_gap, int64_t min_run,
+                                     int32_t frame_size, int32_t hop, float on, float off, int64_t pad_before,
+                                     int64_t pad_after, void* state, int64_t* segments, int64_t capacity,
+                                     int64_t* found, int16_t* history, int64_t history_elems, int16_t* voiced,
+                                     int32_t* voiced_len, void* stream) {
+  VAD_SEG_OP_HOST;
+  return stream_segments_entry(true, nullptr, 0, n_streams,
+                               vad_stream_seg_flush_rows_pad(max_gap, min_run, frame_size, hop, pad_before, pad_after),
+                               1, max_gap, min_run, frame_size, hop, state, segments, capacity, found, 2, nullptr, 0,
+                               0, history, history_elems, voiced, voiced_len, stream, &oph);
+}
+#undef VAD_SEG_OP_HOST
 
 // Replay of a captured graph (a hop block with its host copies,
 // vad_amd.stream.StreamBatch.capture): hipGraphLaunch on the caller's stream.

@@ -30,6 +30,7 @@
 // because that unit's tile kernels keep theirs inside their bodies.
 #include "block_scan.h"
 #include "features.h"
+#include "score_dev.h"
 #include "tree_walk.h"
 
 namespace vad {
@@ -49,30 +50,12 @@ int num_cus() {
 // ---------------------------------------------------------------------------
 // FFN scores
 // ---------------------------------------------------------------------------
-// A row of C logits, read as one vector: 4-byte aligned is all a row has when
-// C is odd, and all a global load needs.
-template <int C>
-struct __attribute__((packed, aligned(4))) LogitRow {
-  float z[C];
-};
-
 template <int C>
 __global__ __launch_bounds__(256) void logit_scores_kernel(const float* __restrict__ logits, int64_t n, int active,
                                                            float* __restrict__ scores) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const LogitRow<C> r = *reinterpret_cast<const LogitRow<C>*>(logits + i * C);
-    float za = r.z[0];
-#pragma unroll
-    for (int j = 1; j < C; ++j) za = j == active ? r.z[j] : za;
-    float sum = 0.f;
-    bool finite = true;
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-      finite &= fabsf(r.z[j]) < INFINITY;  // false for inf and NaN
-      const float e = expf(r.z[j] - za);
-      sum += j == active ? 0.f : e;
-    }
-    scores[i] = finite ? 1.0f / (1.0f + sum) : 0.f;
+    scores[i] = softmax_score<C>(r.z, active);  // score_dev.h: the hop kernel's function too
   }
 }
 

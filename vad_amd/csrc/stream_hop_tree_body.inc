@@ -1,0 +1,285 @@
+// The body of the tree hop kernels (stream_tree_kernel.hip), included once per
+// kernel: stream_hop_tree_kernel with VAD_HOP_SCORE 0 -- the label-only
+// kernel, token for token what it was before there were scores, hence its
+// instructions (profiles/stream_scores/isa.md) -- and
+// stream_hop_tree_scores_kernel with VAD_HOP_SCORE 1, which also writes, per
+// hop, node_score[leaf] of the leaf NODE the walk ends in (the stream form of
+// score_kernel.hip's tree_window_score_kernel; node 0 for a malformed table,
+// as tree_walk_node) to scores[k * score_kstride + s], NaN for a hop that has
+// no window yet.  The score table is NOT staged: a hop reads one entry of it,
+// by lane 0, from global memory.  Staging 4 B per node beside the 16-B nodes
+// would take a fifth of the LDS the node table may use (fewer trees walked
+// from LDS) to save one L2 read per hop, and the global walk has no staged
+// table to put it beside.
+  extern __shared__ __attribute__((aligned(16))) float hsm[];
+  const int waves = blockDim.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  // -- stage the MFCC plan's hop blob, then the compact node table (one node
+  // per lane and DMA), by LDS-DMA; then request the stream's state and the
+  // FFT's twiddles (registers); then the block's only barrier
+  float* base = hsm + waves * kHopWaveFloats;
+  {
+    const float4* m4 = reinterpret_cast<const float4*>(blob);
+    const float4* t4 = reinterpret_cast<const float4*>(cnodes);
+    const int nm4 = blob_n >> 2, n4 = nm4 + lds_nodes;
+    for (int c0 = wv * 64; c0 < n4; c0 += (int)blockDim.x) {  // wave-uniform chunk base
+      const int c = c0 + lane;
+      if (c < n4)
+        __builtin_amdgcn_global_load_lds(c < nm4 ? (const void*)(m4 + c) : (const void*)(t4 + (c - nm4)),
+                                         (__attribute__((address_space(3))) void*)(base + 4 * c0), 16, 0, 0);
+    }
+  }
+  HopTables T;
+  T.tw = reinterpret_cast<const float2*>(base);
+  const int* ilo = reinterpret_cast<const int*>(base + 2 * 256);
+  T.f_lo = ilo;
+  T.f_len = ilo + nf;
+  T.f_off = ilo + 2 * nf;
+  T.taps = base + ((2 * 256 + 3 * nf + 3) & ~3);  // 16-B aligned rows of n_taps (a multiple of 4) in all
+  T.dct = T.taps + n_taps;
+  const int4* cn = reinterpret_cast<const int4*>(base + blob_n);  // {thr bits, feature, left, right}
+
+  const int64_t s = (int64_t)blockIdx.x * waves + wv;
+  const int64_t sc = s < n_streams ? s : 0;
+  // -- the stream's state, requested before the barrier so its latency
+  // overlaps the staging
+  float* row = frames + sc * fstride;
+  const int keep = len - hlen;
+  float v[NR], hn[NR];
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int t = lane + 64 * i;
+    v[i] = t < len ? row[t] : 0.f;
+    hn[i] = (t >= keep && t < len) ? (float)hop[sc * hstride + (t - keep)] : 0.f;
+  }
+  int c = count[sc];
+  float* rs = ring + sc * 5 * mfcc_n;
+  float rv[5];
+#pragma unroll
+  for (int d = 0; d < 5; ++d) rv[d] = lane < mfcc_n ? rs[d * mfcc_n + lane] : 0.f;
+  // this lane's FFT twiddles (stream_hop_kernel: registers in the 7-chunk
+  // build, the staged table in the 16-chunk one)
+  const float2* tw_g = reinterpret_cast<const float2*>(blob);
+  constexpr bool kTwReg = NR <= 7;
+  float2 twr[3][3], tws[4];
+  if constexpr (kTwReg) {
+#pragma unroll
+    for (int st = 1; st < 4; ++st) {
+      const int ns = 1 << (2 * st);
+      const int m = (lane & (ns - 1)) * (64 >> (2 * st));
+#pragma unroll
+      for (int jj = 1; jj < 4; ++jj) twr[st - 1][jj - 1] = w256(tw_g, jj * m);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tws[q] = tw_g[lane + 64 * q];
+  }
+  // the staged tables are complete: LDS-DMA writes count on vmcnt, not
+  // lgkmcnt, and a workgroup-scope release fence need not drain vmcnt, so the
+  // wait is explicit (vmcnt 0, before the barrier)
+  __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt 0, expcnt 7, lgkmcnt 15
+  __syncthreads();
+  if (s >= n_streams) return;  // wave-uniform; no barrier below
+  float* scr = hsm + wv * kHopWaveFloats;
+  float2* z0 = reinterpret_cast<float2*>(scr);
+  float2* z1 = reinterpret_cast<float2*>(scr + kHopZ);
+  float* lmr = scr + 2 * kHopZ;
+  float* act_a = lmr + kMaxFilters;
+  float* fb = scr;  // the frame shift goes through the FFT buffers (2 kHopZ >= 1024 floats)
+  const int used = len < kFftN ? len : kFftN;
+
+  for (int k = 0; k < n_hops; ++k) {
+    // the lane index, opaque per hop (stream_hop_kernel: keeps the hop's LDS
+    // addresses out of registers across hops)
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    // -- frame: shift by the hop through LDS, append the new samples
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      const int t = ln + 64 * i;
+      if (t < len) fb[t] = v[i];
+    }
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      const int t = ln + 64 * i;
+      v[i] = t < keep ? fb[t + hlen] : hn[i];
+    }
+    asm volatile("" ::: "memory");
+    if (k + 1 < n_hops) {  // the next hop's samples, in flight during this one
+      const TH* hs = hop + (int64_t)(k + 1) * hop_kstride + s * hstride;
+#pragma unroll
+      for (int i = 0; i < NR; ++i) {
+        const int t = ln + 64 * i;
+        hn[i] = (t >= keep && t < len) ? (float)hs[t - keep] : 0.f;
+      }
+    }
+    uint8_t* lab_k = labels + (int64_t)k * lab_kstride;
+    // samples of the FFT (np.fft.fft(x, 512): zero-pad / truncate, mfcc.py:61)
+    float* xs = reinterpret_cast<float*>(z1);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {  // all 512 inputs: the zero padding past the frame too
+      const int t = ln + 64 * i;  // sample t = component t & 1 of complex t / 2
+      xs[2 * zp(t >> 1) + (t & 1)] = (i < NR && t < used) ? v[i < NR ? i : 0] : 0.f;
+    }
+    asm volatile("" ::: "memory");
+
+    // -- 256-point complex FFT, Stockham radix-4
+    float2* src = z1;
+    float2* dst = z0;
+#pragma unroll
+    for (int st = 0; st < 4; ++st) {
+      const int ns = 1 << (2 * st);  // 1, 4, 16, 64
+      const int kk = ln & (ns - 1);
+      float2 a0 = src[zp(ln)], a1 = src[zp(ln + 64)], a2 = src[zp(ln + 128)], a3 = src[zp(ln + 192)];
+      if (st > 0) {  // W_{4 ns}^(j k) = W256^(64 j k / ns)
+        const int m = kk * (64 >> (2 * st));
+        a1 = cmulf(a1, kTwReg ? twr[st - 1][0] : w256(T.tw, m));
+        a2 = cmulf(a2, kTwReg ? twr[st - 1][1] : w256(T.tw, 2 * m));
+        a3 = cmulf(a3, kTwReg ? twr[st - 1][2] : w256(T.tw, 3 * m));
+      }
+      const float2 b0 = make_float2(a0.x + a2.x, a0.y + a2.y), b1 = make_float2(a0.x - a2.x, a0.y - a2.y);
+      const float2 b2 = make_float2(a1.x + a3.x, a1.y + a3.y), b3 = make_float2(a1.x - a3.x, a1.y - a3.y);
+      const int o = (ln >> (2 * st)) * (4 * ns) + kk;
+      dst[zp(o)] = make_float2(b0.x + b2.x, b0.y + b2.y);
+      dst[zp(o + ns)] = make_float2(b1.x + b3.y, b1.y - b3.x);      // b1 - i b3
+      dst[zp(o + 2 * ns)] = make_float2(b0.x - b2.x, b0.y - b2.y);
+      dst[zp(o + 3 * ns)] = make_float2(b1.x - b3.y, b1.y + b3.x);  // b1 + i b3
+      float2* t = src;
+      src = dst;
+      dst = t;
+      asm volatile("" ::: "memory");
+    }
+    // -- real-FFT split: 2X[k] = S - i W512^k D; |2X|^2 into the free buffer
+    float* pw = reinterpret_cast<float*>(dst);
+    float pk[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int kb = ln + 64 * q;
+      const float2 zk = src[zp(kb)], zn = src[zp((256 - kb) & 255)];
+      const float2 S = make_float2(zk.x + zn.x, zk.y - zn.y);
+      const float2 D = make_float2(zk.x - zn.x, zk.y + zn.y);
+      const float2 Tw = cmulf(D, kTwReg ? tws[q] : T.tw[kb]);
+      const float u = S.x + Tw.y, vv = S.y - Tw.x;
+      pk[q] = fmaf(u, u, vv * vv);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) pw[ln + 64 * q] = pk[q];
+    asm volatile("" ::: "memory");
+    // -- mel + log10 (ln m), lifter x DCT (ln c)
+    if (ln < nf) {
+      const int lo4 = T.f_lo[ln], n4 = T.f_len[ln];
+      const float4* wt4 = reinterpret_cast<const float4*>(T.taps + T.f_off[ln]);
+      const float4* pw4 = reinterpret_cast<const float4*>(pw + lo4);
+      float e = 0.f;
+#pragma unroll 2
+      for (int t = 0; t < n4; t += 4) {
+        const float4 w = wt4[t >> 2], q = pw4[t >> 2];
+        e = fmaf(w.x, q.x, e);
+        e = fmaf(w.y, q.y, e);
+        e = fmaf(w.z, q.z, e);
+        e = fmaf(w.w, q.w, e);
+      }
+      lmr[ln] = log10_pos(e == 0.f ? 0x1p-52f : e);  // mfcc.py:74-75
+    }
+    asm volatile("" ::: "memory");
+    float mf = 0.f;
+    if (ln < mfcc_n) {
+      const float4* d4 = reinterpret_cast<const float4*>(T.dct + ln * vec_row_stride(nf));
+      const float4* l4 = reinterpret_cast<const float4*>(lmr);
+      int m = 0;
+#pragma unroll 4
+      for (; m + 4 <= nf; m += 4) {
+        const float4 d = d4[m >> 2], l = l4[m >> 2];
+        mf = fmaf(d.x, l.x, mf);
+        mf = fmaf(d.y, l.y, mf);
+        mf = fmaf(d.z, l.z, mf);
+        mf = fmaf(d.w, l.w, mf);
+      }
+      const float* d = T.dct + ln * vec_row_stride(nf);
+      for (; m < nf; ++m) mf = fmaf(d[m], lmr[m], mf);
+    }
+    // -- window of the five previous frames, then push the new row
+    const bool have = c >= 5;
+    act_a[ln] = 0.f;  // the feature row, zeroed before the store as in stream_hop_kernel
+    asm volatile("" ::: "memory");
+    if (ln < mfcc_n) {
+      if (have) {
+        // slot (c + d) % 5, d = 0..4: the ring in arrival order, oldest first
+        float r[5];
+#pragma unroll
+        for (int d = 0; d < 5; ++d) {
+          const int q = (c + d) % 5;
+          r[d] = q == 0 ? rv[0] : q == 1 ? rv[1] : q == 2 ? rv[2] : q == 3 ? rv[3] : rv[4];
+        }
+        const Feat3 ft = feature_triple(r[0], r[1], r[2], r[3], r[4], VAD_FEAT_ANALYSER);
+        act_a[ln] = ft.mn;
+        act_a[mfcc_n + ln] = ft.d1;
+        act_a[2 * mfcc_n + ln] = ft.d2;
+      }
+      const int q = c % 5;  // the push (ring slot of the oldest row)
+#pragma unroll
+      for (int d = 0; d < 5; ++d) rv[d] = q == d ? mf : rv[d];
+    }
+    asm volatile("" ::: "memory");
+    // -- the tree: one path for the whole wave.  A node's feature index is
+    // below the plan's n_features <= 3 mfcc_n (checked by the C entry and by
+    // vad_tree_plan_create), its children inside the table; the loop is
+    // bounded by n_nodes so that a malformed table cannot spin (tree_walk)
+    int label = 255;
+#if VAD_HOP_SCORE
+    int leaf = 0;  // the node the walk ends in
+#endif
+    if (have) {
+      int node = 0;
+      label = 0;
+      if (lds_nodes > 0) {
+        for (int it = 0; it < n_nodes; ++it) {
+          const int4 nd = cn[node];
+          const int f = __builtin_amdgcn_readfirstlane(nd.y);
+          if (f < 0) {
+            label = -1 - f;
+#if VAD_HOP_SCORE
+            leaf = node;
+#endif
+            break;
+          }
+          const float xv = act_a[f & 0xffff];
+          const bool left = xv != xv ? (f >> 30) != 0 : xv <= __int_as_float(nd.x);
+          node = __builtin_amdgcn_readfirstlane(left ? nd.z : nd.w);
+        }
+      } else {
+        for (int it = 0; it < n_nodes; ++it) {
+          const TreeNode nd = nodes[node];
+          const int f = __builtin_amdgcn_readfirstlane(nd.feature);
+          if (f < 0) {
+            label = nd.leaf;
+#if VAD_HOP_SCORE
+            leaf = node;
+#endif
+            break;
+          }
+          const float xv = act_a[f];
+          const bool left = xv != xv ? nd.nan_left != 0 : (double)xv <= nd.threshold;
+          node = __builtin_amdgcn_readfirstlane(left ? nd.left : nd.right);
+        }
+      }
+    }
+    if (ln == 0) lab_k[s] = (uint8_t)label;
+#if VAD_HOP_SCORE
+    if (ln == 0) scores[(int64_t)k * score_kstride + s] = have ? node_score[leaf] : __builtin_nanf("");
+#endif
+    c = ring_count_next(c);
+    asm volatile("" ::: "memory");
+  }
+  // -- the stream's state back: frame, ring, count
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int t = lane + 64 * i;
+    if (t < len) row[t] = v[i];
+  }
+  if (lane < mfcc_n) {
+#pragma unroll
+    for (int d = 0; d < 5; ++d) rs[d * mfcc_n + lane] = rv[d];
+  }
+  if (lane == 0) count[s] = c;

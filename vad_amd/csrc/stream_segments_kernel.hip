@@ -32,6 +32,31 @@
 // (confirmation: >= r0 - j with r0 > n - max_gap - min_run),
 // which is why c[d] is read off the queue without looking ahead.
 //
+// Operating point (stream_segments_op_kernel; the clip chain of
+// score_kernel.hip, hysteresis -> smooth -> dilate -> segments, one window at
+// a time).  The block holds scores or labels.
+//   hysteresis  h = 1 at s >= on, 0 at s < off or NaN, else the previous h
+//               (0 before the first window); a = h.  One bit of the state.
+//   padding     a confirmed run [r0, r1] is queued and joined as
+//               [max(r0 - pad_before, 0), r1 + pad_after]: the join test is
+//               (r0 - pad_before) - end - 1 <= j against the newest segment's
+//               padded end, and that end follows r1 + pad_after.  A flush
+//               knows the window count N and stops the newest end at N - 1.
+//   delay       D = max_gap + max(min_run, 1) + j + 1 + pad_before.  A run is
+//               confirmed at a window n <= r0 + max(min_run, 1) + max_gap - 1
+//               and then changes windows >= r0 - pad_before - j (its padded
+//               start, or the gap of <= j windows it closes), which is
+//               > n - D.  Growing a confirmed run moves an end forward from
+//               r1 + pad_after: windows > r1 >= n - max_gap - 1 > n - D, so
+//               pad_after adds no delay.  c[d], d = n - D, is therefore final.
+//   queue       two queued segments come from runs whose starts are at least
+//               max(min_run, 1) + max_gap + 1 apart; after the finished one
+//               left, the oldest ends at >= d, so every younger run starts at
+//               r0 >= d + pad_before + j + 2 = n - max_gap - max(min_run, 1) + 1
+//               and was confirmed, r0 <= n - max(min_run, 1) + 1: max_gap + 1
+//               places, less than the spacing, hold one start.  Two queued
+//               after a step, three within it; the four places still suffice.
+//
 // Audio.  Clip position p of a stream lives at history[(p - (L - H)) mod R]
 // of its slice of R elements; positions below L - H (the carried samples) at
 // the slice's top, zero unless the host put the carry there.  A launch first
@@ -54,148 +79,44 @@ struct SegStreamState {
   int32_t cand, conf, nq;
   int32_t wpos;      // history index of the next hop's first sample
   int32_t ended;     // flushed: every further row is empty until the state is zeroed
-  int32_t pad[3];
+  int32_t hyst;      // the operating-point forms' hysteresis decision h (one bit; 0 before the first window)
+  int32_t pad[2];
 };
 static_assert(sizeof(SegStreamState) == kSegStreamStateBytes, "the sizing entry's bytes per stream");
 
 constexpr int kSegStreamWaves = 4;
 
+
+// The body is stream_segments_body.inc, included by the label kernel and by
+// the operating-point kernel (SCORES: the block holds fp32 scores).
 template <class T, bool AUDIO>
 __global__ __launch_bounds__(64 * kSegStreamWaves) void stream_segments_kernel(SegStreamArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t s = (int64_t)blockIdx.x * kSegStreamWaves + wv;
-  if (s >= a.n_streams) return;  // wave-uniform; there is no barrier below
-  SegStreamState* sp = static_cast<SegStreamState*>(a.state) + s;
-  SegStreamState st = *sp;
-  int64_t found = a.found[s];
-  const int H = a.hop, L = a.frame_size, R = a.ring;
-  // a state that was never zeroed must not become an address
-  if ((uint32_t)st.wpos >= (uint32_t)R) st.wpos = 0;
-  if ((uint32_t)st.nq > 4u) st.nq = 0;
-  const bool flush = a.labels == nullptr;
-  const bool live = st.ended == 0;
-  T* ring = AUDIO ? static_cast<T*>(a.history) + s * (int64_t)R : nullptr;
+#define VAD_SEG_OP 0
+#include "stream_segments_body.inc"
+#undef VAD_SEG_OP
+}
 
-  if (AUDIO && live && !flush) {
-    // -- the block's new samples into the history
-    int w = st.wpos;
-    for (int k = 0; k < a.n_hops; ++k) {
-      const T* h = static_cast<const T*>(a.hop_samples) + (int64_t)k * a.hop_kstride + s * a.hstride;
-      for (int i = lane; i < H; i += 64) {
-        int p = w + i;
-        if (p >= R) p -= R;
-        ring[p] = h[i];
-      }
-      w += H;
-      if (w >= R) w -= R;
-    }
-    // the prefixes below may read them: other lanes' stores of this wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
-  // the prefix of hop t starts L + (D+2)H elements behind that hop's samples
-  const int back = (int)(L + (a.delay + 2) * H);  // <= R (checked by the entry)
-  const int64_t m1 = a.min_run > 1 ? a.min_run : 1;
-
-  for (int k = 0; k < a.n_hops; ++k) {
-    int len = 0;
-    if (live) {
-      const int64_t t = st.t;
-      if (t >= 5) {
-        const int64_t n = t - 5;
-        const bool act = !flush && a.labels[(int64_t)k * a.lab_kstride + s] == a.active;
-        if (act) {
-          if (!st.cand) {
-            st.cand = 1;
-            st.conf = 0;
-            st.r0 = n;
-          }
-          st.r1 = n;
-          if (st.conf) {
-            st.q[0][1] = n;
-          } else if (st.r1 - st.r0 + 1 >= m1) {
-            st.conf = 1;
-            if (st.nq > 0 && st.r0 - st.q[0][1] - 1 <= a.join) {
-              st.q[0][1] = n;
-            } else {
-#pragma unroll
-              for (int i = 3; i > 0; --i) {
-                st.q[i][0] = st.q[i - 1][0];
-                st.q[i][1] = st.q[i - 1][1];
-              }
-              st.q[0][0] = st.r0;
-              st.q[0][1] = n;
-              if (st.nq < 4) ++st.nq;  // never full (see above); if it were, the oldest would go
-            }
-          }
-        } else if (st.cand && n - st.r1 > a.max_gap) {
-          st.cand = 0;
-          st.conf = 0;
-        }
-        const int64_t d = n - a.delay;
-        if (d >= 0) {
-          int64_t o0 = 0, o1 = -1;  // the oldest queued segment
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if (st.nq == i + 1) {
-              o0 = st.q[i][0];
-              o1 = st.q[i][1];
-            }
-          if (st.nq > 0 && o1 < d) {  // finished: window o1 + 1 is decided and inactive
-            if (found >= 0 && found < a.capacity && lane == 0) {
-              int64_t* row = a.segments + (s * a.capacity + found) * 2;
-              row[0] = (o0 + 2) * H;
-              row[1] = (o1 + 2) * H + L;
-            }
-            ++found;
-            --st.nq;
-            o0 = 0, o1 = -1;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-              if (st.nq == i + 1) {
-                o0 = st.q[i][0];
-                o1 = st.q[i][1];
-              }
-          }
-          if (st.nq > 0 && o0 <= d && d <= o1) st.e1 = d + 1;
-          if (st.e1 > 0) {
-            // (e+2)H + L - (d+2)H, clamped to [0, H]
-            const int64_t v = (st.e1 - 1 - d) * H + L;
-            len = v < 0 ? 0 : (v > H ? H : (int)v);
-          }
-        }
-      }
-      if (AUDIO) {
-        if (len > 0) {
-          int r = st.wpos - back;
-          if (r < 0) r += R;
-          T* out = static_cast<T*>(a.voiced) + ((int64_t)k * a.n_streams + s) * H;
-          for (int i = lane; i < len; i += 64) {
-            int p = r + i;
-            if (p >= R) p -= R;
-            out[i] = ring[p];
-          }
-        }
-        st.wpos += H;
-        if (st.wpos >= R) st.wpos -= R;
-      }
-      st.t = t + 1;
-    }
-    if (AUDIO && lane == 0) a.voiced_len[(int64_t)k * a.n_streams + s] = len;
-  }
-  if (flush) st.ended = 1;
-  if (lane == 0) {
-    *sp = st;
-    a.found[s] = found;
-  }
+template <class T, bool AUDIO, bool SCORES>
+__global__ __launch_bounds__(64 * kSegStreamWaves) void stream_segments_op_kernel(SegStreamArgs a, SegOpArgs op) {
+#define VAD_SEG_OP 1
+#include "stream_segments_body.inc"
+#undef VAD_SEG_OP
 }
 
 template <class T, bool AUDIO>
 hipError_t launch_t(const SegStreamArgs& a, hipStream_t st) {
   const dim3 grid((unsigned)((a.n_streams + kSegStreamWaves - 1) / kSegStreamWaves));
   hipLaunchKernelGGL((stream_segments_kernel<T, AUDIO>), grid, dim3(64 * kSegStreamWaves), 0, st, a);
+  return hipGetLastError();
+}
+
+template <class T, bool AUDIO>
+hipError_t launch_op_t(const SegStreamArgs& a, const SegOpArgs& op, hipStream_t st) {
+  const dim3 grid((unsigned)((a.n_streams + kSegStreamWaves - 1) / kSegStreamWaves));
+  if (op.is_scores)
+    hipLaunchKernelGGL((stream_segments_op_kernel<T, AUDIO, true>), grid, dim3(64 * kSegStreamWaves), 0, st, a, op);
+  else
+    hipLaunchKernelGGL((stream_segments_op_kernel<T, AUDIO, false>), grid, dim3(64 * kSegStreamWaves), 0, st, a, op);
   return hipGetLastError();
 }
 
@@ -206,6 +127,15 @@ hipError_t launch_stream_segments(const SegStreamArgs& a, int audio_bytes, hipSt
   if (audio_bytes == 4) return launch_t<float, true>(a, st);
   if (audio_bytes == 2) return launch_t<int16_t, true>(a, st);
   return launch_t<int16_t, false>(a, st);
+}
+
+// The operating-point forms: a.labels is the block (scores or labels, by
+// op.is_scores; nullptr: flush) and a.delay already holds the padded delay.
+hipError_t launch_stream_segments_op(const SegStreamArgs& a, const SegOpArgs& op, int audio_bytes, hipStream_t st) {
+  if (a.n_streams <= 0 || a.n_hops <= 0) return hipSuccess;
+  if (audio_bytes == 4) return launch_op_t<float, true>(a, op, st);
+  if (audio_bytes == 2) return launch_op_t<int16_t, true>(a, op, st);
+  return launch_op_t<int16_t, false>(a, op, st);
 }
 
 }  // namespace vad

@@ -150,6 +150,12 @@ hipError_t launch_stream_hop(const float* blob, int blob_n, int nf, int n_taps,
                              const void* hop, int hop_bytes, int64_t hstride, int hlen, int64_t n_streams,
                              int mfcc_n, float* ring, int* count, uint8_t* labels, int n_hops,
                              int64_t hop_kstride, int64_t lab_kstride, hipStream_t st);
+// the scored hop kernel: also scores[k * score_kstride + s], class `active`
+hipError_t launch_stream_hop_scores(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net,
+                                    float* frames, int64_t fstride, int len, const void* hop, int hop_bytes,
+                                    int64_t hstride, int hlen, int64_t n_streams, int mfcc_n, float* ring, int* count,
+                                    uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride, int active,
+                                    float* scores, int64_t score_kstride, hipStream_t st);
 hipError_t launch_stream_push(float* frames, int64_t fstride, int len, const void* hop, int hop_bytes,
                               int64_t hstride, int hlen, int64_t n_streams, hipStream_t st);
 // The hop kernel and the ring step with the decision tree
@@ -162,6 +168,13 @@ hipError_t launch_stream_hop_tree(const float* blob, int blob_n, int nf, int n_t
                                   int64_t fstride, int len, const void* hop, int hop_bytes, int64_t hstride, int hlen,
                                   int64_t n_streams, int mfcc_n, float* ring, int* count, uint8_t* labels, int n_hops,
                                   int64_t hop_kstride, int64_t lab_kstride, hipStream_t st);
+hipError_t launch_stream_hop_tree_scores(const float* blob, int blob_n, int nf, int n_taps, const TreeNodeC* cnodes,
+                                         const TreeNode* nodes, int n_nodes, bool force_global, float* frames,
+                                         int64_t fstride, int len, const void* hop, int hop_bytes, int64_t hstride,
+                                         int hlen, int64_t n_streams, int mfcc_n, float* ring, int* count,
+                                         uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
+                                         const float* node_score, float* scores, int64_t score_kstride,
+                                         hipStream_t st);
 hipError_t launch_stream_tree_ring(const TreeNodeC* cnodes, int n_nodes, const float* newrow, float* ring, int* count,
                                    int64_t n_streams, int mfcc_n, uint8_t* labels, hipStream_t st);
 hipError_t launch_preemphasis(const float* x, float* y, int64_t n_rows, int64_t row_len, int64_t stride, float a,
@@ -191,6 +204,15 @@ struct SegStreamArgs {
   int32_t* voiced_len;
 };
 hipError_t launch_stream_segments(const SegStreamArgs& a, int audio_bytes, hipStream_t st);
+// The operating-point forms: a.labels is the (n_hops, n_streams) block of
+// fp32 scores (is_scores; hysteresis on / off) or of uint8 labels, a.delay
+// includes pad_before, and a confirmed run is padded before it is queued.
+struct SegOpArgs {
+  float on, off;
+  int is_scores;
+  int64_t pad_before, pad_after;  // windows
+};
+hipError_t launch_stream_segments_op(const SegStreamArgs& a, const SegOpArgs& op, int audio_bytes, hipStream_t st);
 // any fft_n other than 512 (spec_generic.hip): mode 0 frames -> MFCC,
 // 1 frames -> spectra, 2 spectra -> MFCC; tw = exp(-2 pi i m / fft_n), fp64
 hipError_t launch_generic(int mode, const MfccDev* plan, const float* src, int64_t stride, int len, int64_t n,

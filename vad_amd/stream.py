@@ -46,6 +46,19 @@ half the bytes.  The kernels convert with an exact (float) on load; frames,
 ring and counts stay fp32, so labels and state equal the fp32 batch's bit
 for bit.
 
+Scores: StreamBatch(..., scores=True, active=1) also keeps a static
+``score_block`` (K, S) float32 next to ``label_block``: per hop and stream the
+classifier's estimate in [0, 1] that the window is of class index ``active``
+-- the FFN's softmax (vad_amd.scores.scores_from_logits' function) or the
+tree leaf's class share (TreeClassifier.score_table) -- NaN where the label
+is 255.  The hop kernel writes it (vad_stream_hops_scores and its _i16 /
+tree forms: still one kernel, so a captured one-hop step stays one node) in
+step, step_block (both layouts, in place) and graph replay; labels and state
+equal those of a batch without scores.  kernel="three" has no scores.  The
+host forms (step_host, HostPipeline) copy labels only: the scores stay on the
+device, in ``score_block``, valid once the step has run.  segmenter(on=...,
+off=..., pad=...) feeds them to the online segmenter.
+
 Blocks in flight: host_pipeline(depth) returns a HostPipeline with `depth`
 slots, each with pinned host buffers and a device input / label block of its
 own, and three streams (copy-in, compute, copy-out): submit(d) enqueues slot
@@ -101,7 +114,7 @@ class StreamBatch:
     "global" always walks from global memory (same labels)."""
 
     def __init__(self, n_streams, ffn, cfg: MfccConfig = MfccConfig(), device=None, kernel="hop",
-                 hops_per_step=1, input_dtype=torch.float32, tree_walk="auto"):
+                 hops_per_step=1, input_dtype=torch.float32, tree_walk="auto", scores=False, active=1):
         if input_dtype not in (torch.float32, torch.int16):
             raise ValueError("input_dtype must be torch.float32 or torch.int16")
         if tree_walk not in _TREE_WALKS:
@@ -120,6 +133,13 @@ class StreamBatch:
             raise ValueError("kernel must be 'hop' or 'three'")
         if kernel == "hop" and cfg.window is not None:
             raise ValueError("the one-kernel hop has no analysis window; use kernel='three'")
+        self.scores, self.active = bool(scores), int(active)
+        if self.scores:
+            if kernel == "three":
+                raise ValueError("scores come from the one-kernel hop: kernel='three' has none")
+            n_cls = ffn.score_classes() if self.is_tree else int(ffn.layers[-1][1].shape[0])
+            if not 0 <= self.active < n_cls:
+                raise ValueError(f"active must be a class index below {n_cls}, got {active}")
         self.cfg, self.ffn, self.n, self.kernel = cfg, ffn, int(n_streams), kernel
         self.classifier = ffn
         self.plan = MfccPlan.from_config(cfg)
@@ -141,6 +161,7 @@ class StreamBatch:
         self.count = torch.zeros((S,), dtype=torch.int32, device=dev)
         self.label_block = torch.full((K, S), 255, dtype=torch.uint8, device=dev)
         self.labels = self.label_block[K - 1]
+        self.score_block = torch.full((K, S), float("nan"), dtype=torch.float32, device=dev) if self.scores else None
         self.scratch = torch.zeros((S, C), dtype=torch.float32, device=dev)
         self.graph = None
         self.graph_host_io = False
@@ -158,6 +179,8 @@ class StreamBatch:
         self.ring.zero_()
         self.count.zero_()
         self.label_block.fill_(255)
+        if self.scores:
+            self.score_block.fill_(float("nan"))
 
     def _hop_call(self, h, n_hops=1, labels=None, stream=None):
         """vad_stream_hops (_i16 for an int16 batch) with the per-batch
@@ -168,7 +191,11 @@ class StreamBatch:
         if getattr(self, "_hop_head", None) is None:
             L = self.cfg.frame_size
             self._hop_name = ("vad_stream_hops_tree" if self.is_tree else "vad_stream_hops") + \
-                ("_i16" if self._i16 else "")
+                ("_scores" if self.scores else "") + ("_i16" if self._i16 else "")
+            if self.scores and self.is_tree:
+                self.ffn.plan_with_scores()
+            # rows [0, n_hops) of score_block, whichever label rows the call writes
+            self._hop_scores = (self.active, _lib.ptr(self.score_block), self.n) if self.scores else ()
             self._hop_fn = getattr(_lib.lib(), self._hop_name)
             self._hop_head = (self.plan.handle, self.ffn.plan.handle, _lib.ptr(self.frames), L, L)
             self._hop_mid = (_lib.ptr(self.ring), _lib.ptr(self.count))
@@ -182,7 +209,7 @@ class StreamBatch:
             self._hop_labels[key] = tail
         rc = self._hop_fn(*self._hop_head, ctypes.c_void_p(h.data_ptr()), h.stride(-2), self.cfg.hop, self.n,
                           n_hops, h.stride(0) if h.dim() == 3 else 0, *self._hop_mid, *tail, *self._hop_walk,
-                          _lib.stream_ptr() if stream is None else stream)
+                          *self._hop_scores, _lib.stream_ptr() if stream is None else stream)
         if rc:
             _lib.check(rc, self._hop_name)
 
@@ -301,6 +328,7 @@ class StreamBatch:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         saved = (self.frames.clone(), self.ring.clone(), self.count.clone(), self.label_block.clone())
+        saved_scores = self.score_block.clone() if self.scores else None
         if host_io:
             self.attach_host_io()
             body = self._host_body
@@ -312,6 +340,8 @@ class StreamBatch:
         torch.cuda.synchronize()
         self.frames.copy_(saved[0]); self.ring.copy_(saved[1])
         self.count.copy_(saved[2]); self.label_block.copy_(saved[3])
+        if self.scores:
+            self.score_block.copy_(saved_scores)
         # keep_graph: the captured hipGraph_t stays alive beside its exec, so
         # the replay plan can read its nodes (vad_graph_plan_create: a
         # one-kernel-node graph -- the one-hop step -- is dispatched as its
@@ -343,9 +373,15 @@ class StreamBatch:
     def segmenter(self, **kw):
         """A StreamSegmenter (vad_amd.stream_segments) matching this batch's
         streams, framing, hops per step and input dtype; kw: max_gap, min_run,
-        active, capacity.  Feed it ``label_block`` and ``inputs`` (or the
-        blocks step_block read in place) after each step."""
+        active, capacity, on, off, pad.  Feed it ``label_block`` and ``inputs``
+        (or the blocks step_block read in place) after each step; with ``on``
+        (the batch must have scores=True) feed it ``score_block`` instead, and
+        ``active`` is the batch's."""
         from .stream_segments import StreamSegmenter
+        if kw.get("on") is not None:
+            if not self.scores:
+                raise ValueError("segmenter(on=...) reads score_block: build the batch with scores=True")
+            kw.setdefault("active", self.active)
         return StreamSegmenter(self.n, self.cfg, hops_per_step=self.K, audio_dtype=self.input_dtype,
                                device=self.frames.device, **kw)
 

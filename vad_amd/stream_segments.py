@@ -13,6 +13,16 @@ writes that hop's voiced samples as a prefix of its row of ``voiced``
 samples equal label_segments / voiced_audio on its equivalent clip (the
 carried frame_size - hop samples, then every hop pushed).
 
+Operating point: StreamSegmenter(..., on=, off=, pad=) carries the clip path's
+decision chain (vad_amd.scores: score_labels -> smooth_labels -> dilate_labels
+-> label_segments) through the live path.  With ``on`` set, push() takes the
+(K, S) float32 score block of a StreamBatch built with scores=True and decides
+each window by hysteresis (1 at s >= on, 0 at s < off or NaN, else the
+previous decision); with pad=(before, after) every smoothed run grows by that
+many windows before the segments are cut, which costs ``before`` more windows
+of delay and none for ``after``.  After flush() the rows and voiced samples
+equal that clip chain on the stream's equivalent clip, bit for bit.
+
 No call synchronises except segments().  One kernel per push: capturable
 behind the hop kernel on the same stream.
 """
@@ -36,7 +46,7 @@ class StreamSegmenter:
     only (no history, no voiced outputs)."""
 
     def __init__(self, n_streams, cfg: MfccConfig = MfccConfig(), max_gap=0, min_run=0, active=1, capacity=64,
-                 hops_per_step=1, audio_dtype=None, device=None):
+                 hops_per_step=1, audio_dtype=None, device=None, on=None, off=None, pad=(0, 0)):
         S, K, L, H = int(n_streams), int(hops_per_step), int(cfg.frame_size), int(cfg.hop)
         if S < 1:
             raise ValueError("n_streams must be >= 1")
@@ -52,25 +62,45 @@ class StreamSegmenter:
             raise ValueError("capacity must be >= 0")
         if audio_dtype is not None and audio_dtype not in _AUDIO:
             raise TypeError(f"audio_dtype must be float32, int16 or None, got {audio_dtype}")
+        from .scores import _check_pad, _check_thresholds
+        if on is None and off is not None:
+            raise ValueError("off needs on")
+        self.on, self.off = _check_thresholds(on, off) if on is not None else (None, None)
+        self.pad = _check_pad(pad)
+        # at the defaults the segmenter calls the label entries it always called
+        self._op = on is not None or self.pad != (0, 0)
         lib = _lib.lib()
         self.n, self.K, self.cfg = S, K, cfg
         self.max_gap, self.min_run, self.active, self.capacity = int(max_gap), int(min_run), int(active), int(capacity)
         self.audio_dtype = audio_dtype
-        self._delay = int(lib.vad_stream_seg_delay(self.max_gap, self.min_run, L, H))
-        self.flush_rows = int(lib.vad_stream_seg_flush_rows(self.max_gap, self.min_run, L, H))
+        if self._op:
+            self._delay = int(lib.vad_stream_seg_delay_pad(self.max_gap, self.min_run, L, H, *self.pad))
+            self.flush_rows = int(lib.vad_stream_seg_flush_rows_pad(self.max_gap, self.min_run, L, H, *self.pad))
+        else:
+            self._delay = int(lib.vad_stream_seg_delay(self.max_gap, self.min_run, L, H))
+            self.flush_rows = int(lib.vad_stream_seg_flush_rows(self.max_gap, self.min_run, L, H))
         if self._delay < 0:
-            raise ValueError("max_gap / min_run out of range")
+            raise ValueError("max_gap / min_run / pad out of range")
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.device = dev
         self.state = torch.zeros((S, int(lib.vad_stream_seg_state_bytes(1)) // 8), dtype=torch.int64, device=dev)
         self.table = torch.zeros((S, self.capacity, 2), dtype=torch.int64, device=dev)
         self.found = torch.zeros((S,), dtype=torch.int64, device=dev)
         self._params = (self.max_gap, self.min_run, L, H)
+        self._block_dtype = torch.float32 if on is not None else torch.uint8
+        if self._op:  # block_is_scores ... and the operating point behind the framing
+            self._is_scores = 1 if on is not None else 0
+            self._params += (self.on if on is not None else 0.0, self.off if on is not None else 0.0) + self.pad
+        self._events_fn = "vad_stream_segments_op" if self._op else "vad_stream_segments"
+        self._events_flush_fn = self._events_fn + "_flush"
         self._tables = (_lib.ptr(self.state), _lib.ptr(self.table), self.capacity, _lib.ptr(self.found))
         if audio_dtype is None:
             self.history = self.voiced = self.voiced_len = self.flush_voiced = self.flush_len = None
             return
-        elems = int(lib.vad_stream_seg_history_elems(S, K, self.max_gap, self.min_run, L, H))
+        if self._op:
+            elems = int(lib.vad_stream_seg_history_elems_pad(S, K, self.max_gap, self.min_run, L, H, *self.pad))
+        else:
+            elems = int(lib.vad_stream_seg_history_elems(S, K, self.max_gap, self.min_run, L, H))
         if elems < 0:
             raise ValueError("the history of one stream would pass 2^30 elements")
         self.history = torch.zeros((S, elems // S), dtype=audio_dtype, device=dev)
@@ -78,12 +108,13 @@ class StreamSegmenter:
         self.voiced_len = torch.zeros((K, S), dtype=torch.int32, device=dev)
         self.flush_voiced = torch.zeros((self.flush_rows, S, H), dtype=audio_dtype, device=dev)
         self.flush_len = torch.zeros((self.flush_rows, S), dtype=torch.int32, device=dev)
-        self._fn = "vad_stream_segments_" + _AUDIO[audio_dtype]
-        self._flush_fn = "vad_stream_segments_flush_" + _AUDIO[audio_dtype]
+        self._fn = self._events_fn + "_" + _AUDIO[audio_dtype]
+        self._flush_fn = self._events_flush_fn + "_" + _AUDIO[audio_dtype]
 
     @property
     def delay(self):
-        """D: hop t decides window t - 5 - D (vad_stream_seg_delay)."""
+        """D: hop t decides window t - 5 - D (vad_stream_seg_delay; with an
+        operating point vad_stream_seg_delay_pad: pad_before more)."""
         return self._delay
 
     def reset(self):
@@ -108,8 +139,9 @@ class StreamSegmenter:
     def _check_labels(self, lab):
         if not isinstance(lab, torch.Tensor) or not lab.is_cuda:
             raise TypeError("label_block must be a CUDA (HIP) torch tensor")
-        if lab.dtype != torch.uint8:
-            raise TypeError(f"label_block must be uint8, got {lab.dtype}")
+        if lab.dtype != self._block_dtype:
+            what = "the score block must be float32" if self.on is not None else "label_block must be uint8"
+            raise TypeError(f"{what}, got {lab.dtype}")
         if lab.dim() == 1 and self.K == 1:
             lab = lab.unsqueeze(0)
         if lab.dim() != 2 or lab.shape[1] != self.n or not 1 <= lab.shape[0] <= self.K:
@@ -135,17 +167,19 @@ class StreamSegmenter:
 
     def push(self, label_block, hop_block=None, stream=None):
         """k <= K hops of every stream: label_block (k, S) uint8 as the hop
-        kernels wrote it (strided rows are fine; (S,) for K = 1), hop_block
+        kernels wrote it (strided rows are fine; (S,) for K = 1) -- with ``on``
+        set, the (k, S) float32 score block instead -- hop_block
         (k, S, hop) the samples they read, in any layout vad_stream_hops
         reads in place.  Returns (voiced, voiced_len) -- the static outputs,
         rows [0, k) written -- or None without audio."""
         lab = self._check_labels(label_block)
         k = lab.shape[0]
         lib = _lib.lib()
-        head = (_lib.ptr(lab), lab.stride(0) if k > 1 else 0, self.n, k, self.active) + self._params + self._tables
+        head = (_lib.ptr(lab),) + ((self._is_scores,) if self._op else ()) + \
+            (lab.stride(0) if k > 1 else 0, self.n, k, self.active) + self._params + self._tables
         st = _lib.stream_ptr(stream)
         if hop_block is None:
-            _lib.check(lib.vad_stream_segments(*head, st), "vad_stream_segments")
+            _lib.check(getattr(lib, self._events_fn)(*head, st), self._events_fn)
             return None
         hop = self._check_hops(hop_block, k)
         _lib.check(getattr(lib, self._fn)(*head, _lib.ptr(hop), hop.stride(1), hop.stride(0) if k > 1 else 0,
@@ -158,10 +192,10 @@ class StreamSegmenter:
         None for an events-only segmenter.  The streams are then ended: reset()
         (or zero a stream's slices) before pushing again."""
         lib = _lib.lib()
-        head = (self.n,) + self._params + self._tables
+        head = (self.n,) + ((self._is_scores,) if self._op else ()) + self._params + self._tables
         st = _lib.stream_ptr(stream)
         if self.history is None:
-            _lib.check(lib.vad_stream_segments_flush(*head, st), "vad_stream_segments_flush")
+            _lib.check(getattr(lib, self._events_flush_fn)(*head, st), self._events_flush_fn)
             return None
         _lib.check(getattr(lib, self._flush_fn)(*head, _lib.ptr(self.history), self.history.numel(),
                                                 _lib.ptr(self.flush_voiced), _lib.ptr(self.flush_len), st),

@@ -52,6 +52,16 @@ class TreePlan:
     def handle(self):
         return self._h
 
+    def set_scores(self, table):
+        """The plan's score table (vad_tree_plan_set_scores): (n_classes,
+        n_nodes) float32, row c the score of class index c per node; the
+        scored hop entries read row ``active``."""
+        t = np.ascontiguousarray(table, np.float32)
+        if t.ndim != 2:
+            raise ValueError("the score table must be (n_classes, n_nodes)")
+        check(lib().vad_tree_plan_set_scores(self._h, t.ctypes.data, t.shape[0]), "vad_tree_plan_set_scores")
+        self.score_classes = int(t.shape[0])
+
     def __del__(self):
         h = getattr(self, "_h", None)
         destroy = getattr(self, "_destroy", None)  # bound at creation: module globals
@@ -147,6 +157,21 @@ class TreeClassifier:
         norm = v.sum(axis=1)
         norm[norm == 0.0] = 1.0
         return np.ascontiguousarray((v[:, int(active)] / norm).astype(np.float32))
+
+    def score_classes(self):
+        """Number of classes score_table() knows; ValueError without node values."""
+        v = self.proba if self.proba is not None else self.value
+        if v is None:
+            self.score_table(0)  # raises with the reason
+        return int(np.asarray(v).shape[1])
+
+    def plan_with_scores(self):
+        """``plan`` with every class's score_table() set on it (once), as the
+        scored streaming entries need it."""
+        p = self.plan
+        if getattr(p, "score_classes", 0) == 0:
+            p.set_scores(np.stack([self.score_table(c) for c in range(self.score_classes())]))
+        return p
 
     def window_scores(self, mfcc, mode=_lib.FEAT_ANALYSER, active=1, out=None, stream=None):
         """Scores (float32, device) of every 5-frame window of an MFCC sequence
