@@ -670,6 +670,81 @@ int vad_stream_hops_tree_scores_i16(const vad_mfcc_plan* plan, const vad_tree_pl
                                     float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
                                     int32_t walk, int32_t active, float* scores, int64_t score_block_stride,
                                     void* stream);
+/* Live spectral noise subtraction in the hop kernels.  The reference's live
+ * analyser computes a noise estimate and the subtracted spectrum and then
+ * takes the MFCC from the unsubtracted one (sklearn_analyser.py:84-101,
+ * 122-123); these entries take it from the subtracted spectrum.  Per stream,
+ * beside frames / ring / count, contiguous fp32 arrays in the kernels' units
+ * |2X|^2 (x 2^-20 gives |X/512|^2), all zero = a fresh stream:
+ *   spec_ring   (S, 5, 256)  raw power rows of the last five frames; slot =
+ *                            the MFCC ring's slot of the same frame
+ *   noise_rows  (S, 5, 256)  the noise rows in arrival order, row 0 the oldest
+ *   noise_count (S) int32    rows held, 0..5
+ *   noise_est   (S, 256)     the estimate e in force: the mean m of the rows
+ *                            held, (((r0 + r1) + r2) + ...) / n, low-passed
+ *                            over the bins with the reference's wrap at bin 0:
+ *                            e[0] = alpha m[255] + (1 - alpha) m[0],
+ *                            e[i] = alpha e[i-1] + (1 - alpha) m[i]; fp32, in
+ *                            the order stream_denoise.h states (an affine scan
+ *                            across the wave); all zero with no rows held
+ * One hop: the frame advances, its power row p goes to spec_ring, the MFCC
+ * row is taken from max(p - e, 0) (NaN kept), the window of the five previous
+ * rows is classified as by the plain entries, and, if the stream has a window,
+ * its label is noise_class and update is 1, the RAW row of the window's middle
+ * frame (three hops old) joins noise_rows -- the oldest row dropped past five
+ * -- and e is taken anew, in force from the next hop.  With an all-zero state
+ * and update 0 labels, scores, frames, ring and count are the plain entries',
+ * bit for bit.
+ * Arguments: those of the scored entry of the same classifier and input type,
+ * then the four state arrays, alpha in [0, 1), noise_class, update (0 / 1).
+ * scores may be null (labels only; active and score_block_stride are then not
+ * read, and a tree plan needs no score table).
+ * vad_stream_noise_load(_i16): n = 1..5 frames per stream, frame j of stream s
+ * at frames + s * stream_stride + j * frame_stride (elements), become noise
+ * rows 0..n-1 (the row a hop stores for that frame, bit for bit), the count n
+ * and the estimate: the reference's load_init_inactive_frames.
+ * Refusals (VAD_EINVAL, before any device call): those of the scored entries;
+ * a null state array; two state arrays that overlap; alpha outside [0, 1) or
+ * NaN; noise_class outside the classifier's classes (the FFN's outputs, the
+ * tree's leaf classes); update not 0 / 1; n outside 1..5.  A plan whose fft_n
+ * is not 512, or with an analysis window: VAD_EUNSUPPORTED, as the plain
+ * hop entries. */
+int64_t vad_stream_spec_ring_floats(int64_t n_streams);  /* n_streams * 5 * 256 */
+int64_t vad_stream_noise_rows_floats(int64_t n_streams); /* n_streams * 5 * 256 */
+int64_t vad_stream_noise_est_floats(int64_t n_streams);  /* n_streams * 256 */
+int vad_stream_hops_denoise(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
+                            int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len,
+                            int64_t n_streams, int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count,
+                            uint8_t* labels, int64_t label_block_stride, int32_t active, float* scores,
+                            int64_t score_block_stride, float* spec_ring, float* noise_rows, int32_t* noise_count,
+                            float* noise_est, float alpha, int32_t noise_class, int32_t update, void* stream);
+int vad_stream_hops_denoise_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames,
+                                int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                                int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                                int32_t active, float* scores, int64_t score_block_stride, float* spec_ring,
+                                float* noise_rows, int32_t* noise_count, float* noise_est, float alpha,
+                                int32_t noise_class, int32_t update, void* stream);
+int vad_stream_hops_tree_denoise(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                                 int64_t frame_stride, int32_t frame_len, const float* hop, int64_t hop_stride,
+                                 int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                 float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                                 int32_t walk, int32_t active, float* scores, int64_t score_block_stride,
+                                 float* spec_ring, float* noise_rows, int32_t* noise_count, float* noise_est,
+                                 float alpha, int32_t noise_class, int32_t update, void* stream);
+int vad_stream_hops_tree_denoise_i16(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                                     int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                                     int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                     float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                                     int32_t walk, int32_t active, float* scores, int64_t score_block_stride,
+                                     float* spec_ring, float* noise_rows, int32_t* noise_count, float* noise_est,
+                                     float alpha, int32_t noise_class, int32_t update, void* stream);
+int vad_stream_noise_load(const vad_mfcc_plan* plan, const float* frames, int64_t stream_stride, int64_t frame_stride,
+                          int32_t frame_len, int32_t n, int64_t n_streams, float* noise_rows, int32_t* noise_count,
+                          float* noise_est, float alpha, void* stream);
+int vad_stream_noise_load_i16(const vad_mfcc_plan* plan, const int16_t* frames, int64_t stream_stride,
+                              int64_t frame_stride, int32_t frame_len, int32_t n, int64_t n_streams,
+                              float* noise_rows, int32_t* noise_count, float* noise_est, float alpha, void* stream);
 /* Replay a captured hipGraph (hipGraphExec_t) on `stream`: the per-hop step
  * of a StreamBatch captured with its host I/O (the H2D copy of every
  * stream's new samples from pinned memory, the hop kernel, the D2H copy of

@@ -127,6 +127,19 @@ SIGNATURES = {
     **{"vad_stream_hops_tree_scores" + t: (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32,
                                                    c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp])
        for t in ("", "_i16")},
+    **{"vad_stream_" + n + "_floats": (c_i64, [c_i64]) for n in ("spec_ring", "noise_rows", "noise_est")},
+    # the scored entries' arguments, then spec_ring, noise_rows, noise_count, noise_est, alpha, noise_class, update
+    **{"vad_stream_hops_denoise" + t: (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32, c_i64,
+                                               c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                               c_f32, c_i32, c_i32, c_vp])
+       for t in ("", "_i16")},
+    **{"vad_stream_hops_tree_denoise" + t: (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32,
+                                                    c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp,
+                                                    c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp])
+       for t in ("", "_i16")},
+    **{"vad_stream_noise_load" + t: (c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_f32,
+                                             c_vp])
+       for t in ("", "_i16")},
     "vad_graph_launch": (c_int, [c_vp, c_vp]),
     "vad_graph_plan_create": (c_int, [c_vp, c_vp, c_vp]),
     "vad_graph_plan_launch": (c_int, [c_vp, c_vp]),

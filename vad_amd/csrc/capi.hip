@@ -649,6 +649,7 @@ struct vad_tree_plan {
   int n_features;
   float* score_dev;      // (n_score_classes, n_nodes) node scores, or null (vad_tree_plan_set_scores)
   int n_score_classes;
+  int n_classes;         // 1 + the largest leaf class
 };
 
 int vad_tree_plan_create(int32_t n_nodes, const int32_t* feature, const double* threshold,
@@ -703,6 +704,8 @@ int vad_tree_plan_create(int32_t n_nodes, const int32_t* feature, const double* 
   }
   p->n_nodes = n_nodes;
   p->n_features = n_features;
+  for (const TreeNode& nd : h)
+    if (nd.feature < 0 && nd.leaf + 1 > p->n_classes) p->n_classes = nd.leaf + 1;
   *out = p;
   return VAD_OK;
 }
@@ -1376,6 +1379,167 @@ int vad_stream_step_tree(const vad_mfcc_plan* plan, const vad_tree_plan* tree, c
     VAD_TRY(launch_mfcc(0, plan->dev, launch_spec(plan), frames, frame_stride, frame_len, n_streams, mfcc_scratch, st));
   return (int)launch_stream_tree_ring(tree->cnodes_dev, tree->n_nodes, mfcc_scratch, ring, count, n_streams,
                                       plan->host.mfcc_n, labels, st);
+}
+
+// ---------------------------------------------------------------------------
+// Live spectral noise subtraction in the hop kernels (stream_denoise.h)
+// ---------------------------------------------------------------------------
+int64_t vad_stream_spec_ring_floats(int64_t n_streams) { return n_streams * 5 * (int64_t)kBins; }
+int64_t vad_stream_noise_rows_floats(int64_t n_streams) { return n_streams * kNoiseRows * (int64_t)kBins; }
+int64_t vad_stream_noise_est_floats(int64_t n_streams) { return n_streams * (int64_t)kBins; }
+
+// the state arrays of n_streams streams (the load entry has no spectrum
+// ring): none null, no two overlapping
+static bool denoise_state_ok(int64_t n_streams, bool with_spec, const float* spec_ring, const float* noise_rows,
+                             const int32_t* noise_count, const float* noise_est) {
+  if ((with_spec && !spec_ring) || !noise_rows || !noise_count || !noise_est) return false;
+  struct Span { uintptr_t lo, hi; };
+  const Span a[4] = {
+      {(uintptr_t)spec_ring, (uintptr_t)spec_ring + (size_t)vad_stream_spec_ring_floats(n_streams) * sizeof(float)},
+      {(uintptr_t)noise_rows, (uintptr_t)noise_rows + (size_t)vad_stream_noise_rows_floats(n_streams) * sizeof(float)},
+      {(uintptr_t)noise_est, (uintptr_t)noise_est + (size_t)vad_stream_noise_est_floats(n_streams) * sizeof(float)},
+      {(uintptr_t)noise_count, (uintptr_t)noise_count + (size_t)n_streams * sizeof(int32_t)}};
+  for (int i = with_spec ? 0 : 1; i < 4; ++i)
+    for (int j = i + 1; j < 4; ++j)
+      if (a[i].lo < a[j].hi && a[j].lo < a[i].hi) return false;
+  return true;
+}
+
+static bool denoise_alpha_ok(float alpha) { return alpha >= 0.f && alpha < 1.f; }  // false for NaN
+
+// The checks of the scored entries in their order (scores may be null here:
+// `active` and the score stride are read only with scores), then the denoise
+// arguments; all before any device call.
+static int stream_hops_denoise_entry(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, const vad_tree_plan* tree,
+                                     float* frames, int64_t frame_stride, int32_t frame_len, const void* hop,
+                                     int hop_bytes, int64_t hop_stride, int32_t hop_len, int64_t n_streams,
+                                     int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count,
+                                     uint8_t* labels, int64_t label_block_stride, int32_t walk, int32_t active,
+                                     float* scores, int64_t score_block_stride, float* spec_ring, float* noise_rows,
+                                     int32_t* noise_count, float* noise_est, float alpha, int32_t noise_class,
+                                     int32_t update, void* stream) {
+  if (!plan || (!ffn && !tree) || n_streams < 0 || n_hops < 0 || frame_len <= 0 || frame_len > 1024 || hop_len <= 0 ||
+      hop_len > frame_len || frame_stride < frame_len || hop_stride < hop_len)
+    return VAD_EINVAL;
+  if (tree && walk != VAD_TREE_WALK_AUTO && walk != VAD_TREE_WALK_GLOBAL) return VAD_EINVAL;
+  if (n_hops > 1 && label_block_stride < n_streams) return VAD_EINVAL;
+  if (scores && n_hops > 1 && score_block_stride < n_streams) return VAD_EINVAL;
+  if (n_hops > 1 && !vad_hop_layout_disjoint(n_streams, n_hops, hop_block_stride, hop_stride, hop_len))
+    return VAD_EINVAL;
+  if (!denoise_alpha_ok(alpha) || (update != 0 && update != 1) || noise_class < 0) return VAD_EINVAL;
+  if (!denoise_state_ok(n_streams, true, spec_ring, noise_rows, noise_count, noise_est)) return VAD_EINVAL;
+  // from here on the plans are read
+  if (scores) {
+    if (tree && !tree->score_dev) return VAD_EINVAL;  // vad_tree_plan_set_scores first
+    if (active < 0 || active >= (tree ? tree->n_score_classes : ffn->net.n_classes)) return VAD_EINVAL;
+  }
+  if (noise_class >= (tree ? tree->n_classes : ffn->net.n_classes)) return VAD_EINVAL;
+  if (n_streams == 0 || n_hops == 0) return VAD_OK;
+  if (!frames || !hop || !ring || !count || !labels) return VAD_EINVAL;
+  if ((tree ? tree->n_features : ffn->net.dims[0]) > 3 * plan->host.mfcc_n) return VAD_EINVAL;
+  if (plan->generic()) return VAD_EUNSUPPORTED;  // its FFT is the 256-point Stockham of fft_n = 512
+  if (plan->spec == kSpecWindow) return VAD_EUNSUPPORTED;  // its table blob carries no analysis window
+  const HopDenoise dn = {spec_ring, noise_rows, noise_count, noise_est, alpha, noise_class, update};
+  if (tree)
+    return (int)launch_stream_hop_tree_denoise(
+        plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps, tree->cnodes_dev, tree->nodes_dev,
+        tree->n_nodes, walk == VAD_TREE_WALK_GLOBAL, frames, frame_stride, frame_len, hop, hop_bytes, hop_stride,
+        hop_len, n_streams, plan->host.mfcc_n, ring, count, labels, n_hops, hop_block_stride, label_block_stride,
+        scores ? tree->score_dev + (size_t)active * (size_t)tree->n_nodes : nullptr, scores, score_block_stride, dn,
+        (hipStream_t)stream);
+  return (int)launch_stream_hop_denoise(plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps, ffn->net,
+                                        frames, frame_stride, frame_len, hop, hop_bytes, hop_stride, hop_len,
+                                        n_streams, plan->host.mfcc_n, ring, count, labels, n_hops, hop_block_stride,
+                                        label_block_stride, active, scores, score_block_stride, dn,
+                                        (hipStream_t)stream);
+}
+
+int vad_stream_hops_denoise(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
+                            int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len,
+                            int64_t n_streams, int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count,
+                            uint8_t* labels, int64_t label_block_stride, int32_t active, float* scores,
+                            int64_t score_block_stride, float* spec_ring, float* noise_rows, int32_t* noise_count,
+                            float* noise_est, float alpha, int32_t noise_class, int32_t update, void* stream) {
+  if (!ffn) return VAD_EINVAL;
+  return stream_hops_denoise_entry(plan, ffn, nullptr, frames, frame_stride, frame_len, hop, 4, hop_stride, hop_len,
+                                   n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, 0,
+                                   active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
+                                   alpha, noise_class, update, stream);
+}
+
+int vad_stream_hops_denoise_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames,
+                                int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                                int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                                int32_t active, float* scores, int64_t score_block_stride, float* spec_ring,
+                                float* noise_rows, int32_t* noise_count, float* noise_est, float alpha,
+                                int32_t noise_class, int32_t update, void* stream) {
+  if (!ffn) return VAD_EINVAL;
+  return stream_hops_denoise_entry(plan, ffn, nullptr, frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len,
+                                   n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, 0,
+                                   active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
+                                   alpha, noise_class, update, stream);
+}
+
+int vad_stream_hops_tree_denoise(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                                 int64_t frame_stride, int32_t frame_len, const float* hop, int64_t hop_stride,
+                                 int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                 float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                                 int32_t walk, int32_t active, float* scores, int64_t score_block_stride,
+                                 float* spec_ring, float* noise_rows, int32_t* noise_count, float* noise_est,
+                                 float alpha, int32_t noise_class, int32_t update, void* stream) {
+  if (!tree) return VAD_EINVAL;
+  return stream_hops_denoise_entry(plan, nullptr, tree, frames, frame_stride, frame_len, hop, 4, hop_stride, hop_len,
+                                   n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk,
+                                   active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
+                                   alpha, noise_class, update, stream);
+}
+
+int vad_stream_hops_tree_denoise_i16(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                                     int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                                     int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                     float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                                     int32_t walk, int32_t active, float* scores, int64_t score_block_stride,
+                                     float* spec_ring, float* noise_rows, int32_t* noise_count, float* noise_est,
+                                     float alpha, int32_t noise_class, int32_t update, void* stream) {
+  if (!tree) return VAD_EINVAL;
+  return stream_hops_denoise_entry(plan, nullptr, tree, frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len,
+                                   n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk,
+                                   active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
+                                   alpha, noise_class, update, stream);
+}
+
+// n frames per stream, (S, n, frame_len) with the strides given in elements,
+// become the noise rows 0..n-1, the count n and the estimate
+static int stream_noise_load_entry(const vad_mfcc_plan* plan, const void* frames, int in_bytes, int64_t stream_stride,
+                                   int64_t frame_stride, int32_t frame_len, int32_t n, int64_t n_streams,
+                                   float* noise_rows, int32_t* noise_count, float* noise_est, float alpha,
+                                   void* stream) {
+  if (!plan || n_streams < 0 || frame_len <= 0 || frame_len > 1024 || n < 1 || n > kNoiseRows ||
+      frame_stride < frame_len || stream_stride < (int64_t)(n - 1) * frame_stride + frame_len)
+    return VAD_EINVAL;
+  if (!denoise_alpha_ok(alpha)) return VAD_EINVAL;
+  if (!denoise_state_ok(n_streams, false, nullptr, noise_rows, noise_count, noise_est)) return VAD_EINVAL;
+  if (n_streams == 0) return VAD_OK;
+  if (!frames) return VAD_EINVAL;
+  if (plan->generic()) return VAD_EUNSUPPORTED;
+  if (plan->spec == kSpecWindow) return VAD_EUNSUPPORTED;
+  return (int)launch_stream_noise_load(plan->hop_blob, frames, in_bytes, stream_stride, frame_stride, frame_len, n,
+                                       n_streams, noise_rows, noise_count, noise_est, alpha, (hipStream_t)stream);
+}
+
+int vad_stream_noise_load(const vad_mfcc_plan* plan, const float* frames, int64_t stream_stride, int64_t frame_stride,
+                          int32_t frame_len, int32_t n, int64_t n_streams, float* noise_rows, int32_t* noise_count,
+                          float* noise_est, float alpha, void* stream) {
+  return stream_noise_load_entry(plan, frames, 4, stream_stride, frame_stride, frame_len, n, n_streams, noise_rows,
+                                 noise_count, noise_est, alpha, stream);
+}
+
+int vad_stream_noise_load_i16(const vad_mfcc_plan* plan, const int16_t* frames, int64_t stream_stride,
+                              int64_t frame_stride, int32_t frame_len, int32_t n, int64_t n_streams,
+                              float* noise_rows, int32_t* noise_count, float* noise_est, float alpha, void* stream) {
+  return stream_noise_load_entry(plan, frames, 2, stream_stride, frame_stride, frame_len, n, n_streams, noise_rows,
+                                 noise_count, noise_est, alpha, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -7,6 +7,10 @@
 // the fp32 score of class `active` to scores[k * score_kstride + s]: the
 // softmax of score_dev.h on the wave-uniform logits the argmax reads,
 // computed and stored by lane 0; NaN for a hop that has no window yet.
+// stream_hop_denoise_kernel is the scored form with VAD_HOP_DENOISE 1: the
+// noise estimate comes off the power spectrum before the mel bank, and the
+// windows of the noise class feed it (stream_denoise.h); its `scores` may be
+// null.  With VAD_HOP_DENOISE 0 the text is what it was without it.
   extern __shared__ __attribute__((aligned(16))) float hsm[];
   const int waves = blockDim.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -61,6 +65,18 @@
   float rv[5];
 #pragma unroll
   for (int d = 0; d < 5; ++d) rv[d] = lane < mfcc_n ? rs[d * mfcc_n + lane] : 0.f;
+#if VAD_HOP_DENOISE
+  // the denoise state (stream_denoise.h): the rows held; the spectrum ring,
+  // the noise rows and here the estimate too stay in global memory (the 7-chunk
+  // build has no four registers left to carry the lane's bins of the estimate
+  // across the hops without scratch, as the tree kernel does: each hop reads
+  // them again, 16 B per lane that the lane itself or the launch before wrote)
+  const int64_t dn_s = dn_uniform(sc);  // scalar row addresses: the lane's 16 B offset is the only vector part
+  float* dn_spec = dn.spec + dn_s * (5 * kBins);
+  float* dn_rows = dn.rows + dn_s * (kNoiseRows * kBins);
+  float4* dn_est = reinterpret_cast<float4*>(dn.est + dn_s * kBins);
+  int dn_n = __builtin_amdgcn_readfirstlane(dn.held[sc]);
+#endif
   // this lane's FFT twiddles (W512^k table = the blob's first 256 complex):
   // stage st's radix-4 butterfly multiplies by W256^(j m), m = (lane mod
   // 4^st) 64 / 4^st, j = 1..3; the real-FFT split by W512^(lane + 64 q)
@@ -183,6 +199,12 @@
 #pragma unroll
     for (int q = 0; q < 4; ++q) pw[ln + 64 * q] = pk[q];
     asm volatile("" ::: "memory");
+#if VAD_HOP_DENOISE
+    // -- the raw row into the spectrum ring (the MFCC ring's slot), then the
+    // noise estimate off the power bins, clamped at zero
+    dn_store_subtract(pw, ln, dn_spec + (c % 5) * kBins, dn_est[ln]);
+    asm volatile("" ::: "memory");
+#endif
     // -- mel + log10 (ln m), lifter x DCT (ln c)
     if (ln < nf) {
       // the filter's 16-B aligned tap row against the power bins from its
@@ -289,18 +311,35 @@
                         hin[3 < net.n_classes ? 3 : 0]};
       label = (uint8_t)argmax_classes(zl, net.n_classes);
 #if VAD_HOP_SCORE
+#if VAD_HOP_DENOISE
+      if (ln == 0 && scores) {  // the denoising kernel is the scored form; its scores may be null
+#else
       if (ln == 0) {
+#endif
         const int nc = net.n_classes;
         scores[(int64_t)k * score_kstride + s] = nc == 2   ? softmax_score<2>(zl, active)
                                                  : nc == 3 ? softmax_score<3>(zl, active)
                                                  : nc == 4 ? softmax_score<4>(zl, active)
                                                            : softmax_score<1>(zl, active);
       }
+#if VAD_HOP_DENOISE
+    } else if (ln == 0 && scores) {
+#else
     } else if (ln == 0) {
+#endif
       scores[(int64_t)k * score_kstride + s] = __builtin_nanf("");
 #endif
     }
     if (ln == 0) lab_k[s] = label;
+#if VAD_HOP_DENOISE
+    // -- a window of the noise class: the raw row of its middle frame (three
+    // hops old, slot (c + 2) % 5 of the spectrum ring) joins the noise rows,
+    // and the estimate is taken anew; it holds from the next hop on
+    if (have && dn.update && __builtin_amdgcn_readfirstlane((int)label) == dn.noise_class) {
+      const float4 mid = reinterpret_cast<const float4*>(dn_spec + ((c + 2) % 5) * kBins)[ln];
+      dn_est[ln] = dn_estimate(dn_push_mean(dn_rows, dn_n, mid, ln), dn.alpha, ln);
+    }
+#endif
     c = ring_count_next(c);
     asm volatile("" ::: "memory");
   }
@@ -315,3 +354,6 @@
     for (int d = 0; d < 5; ++d) rs[d * mfcc_n + lane] = rv[d];
   }
   if (lane == 0) count[s] = c;
+#if VAD_HOP_DENOISE
+  if (lane == 0) dn.held[s] = dn_n;
+#endif

@@ -11,6 +11,9 @@
 // would take a fifth of the LDS the node table may use (fewer trees walked
 // from LDS) to save one L2 read per hop, and the global walk has no staged
 // table to put it beside.
+// stream_hop_tree_denoise_kernel is the scored form with VAD_HOP_DENOISE 1
+// (stream_hop_ffn_body.inc says what that adds; `scores`, and with it
+// node_score, may be null).  With VAD_HOP_DENOISE 0 the text is unchanged.
   extern __shared__ __attribute__((aligned(16))) float hsm[];
   const int waves = blockDim.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -58,6 +61,16 @@
   float rv[5];
 #pragma unroll
   for (int d = 0; d < 5; ++d) rv[d] = lane < mfcc_n ? rs[d * mfcc_n + lane] : 0.f;
+#if VAD_HOP_DENOISE
+  // the denoise state (stream_denoise.h): the estimate in force (the lane's
+  // four bins, registers across the hops) and the rows held; the spectrum
+  // ring and the noise rows stay in global memory
+  const int64_t dn_s = dn_uniform(sc);  // scalar row addresses: the lane's 16 B offset is the only vector part
+  float* dn_spec = dn.spec + dn_s * (5 * kBins);
+  float* dn_rows = dn.rows + dn_s * (kNoiseRows * kBins);
+  float4 dn_e = reinterpret_cast<const float4*>(dn.est + dn_s * kBins)[lane];
+  int dn_n = __builtin_amdgcn_readfirstlane(dn.held[sc]);
+#endif
   // this lane's FFT twiddles (stream_hop_kernel: registers in the 7-chunk
   // build, the staged table in the 16-chunk one)
   const float2* tw_g = reinterpret_cast<const float2*>(blob);
@@ -166,6 +179,12 @@
 #pragma unroll
     for (int q = 0; q < 4; ++q) pw[ln + 64 * q] = pk[q];
     asm volatile("" ::: "memory");
+#if VAD_HOP_DENOISE
+    // -- the raw row into the spectrum ring (the MFCC ring's slot), then the
+    // noise estimate off the power bins, clamped at zero
+    dn_store_subtract(pw, ln, dn_spec + (c % 5) * kBins, dn_e);
+    asm volatile("" ::: "memory");
+#endif
     // -- mel + log10 (ln m), lifter x DCT (ln c)
     if (ln < nf) {
       const int lo4 = T.f_lo[ln], n4 = T.f_len[ln];
@@ -266,8 +285,19 @@
       }
     }
     if (ln == 0) lab_k[s] = (uint8_t)label;
-#if VAD_HOP_SCORE
+#if VAD_HOP_DENOISE
+    if (ln == 0 && scores) scores[(int64_t)k * score_kstride + s] = have ? node_score[leaf] : __builtin_nanf("");
+#elif VAD_HOP_SCORE
     if (ln == 0) scores[(int64_t)k * score_kstride + s] = have ? node_score[leaf] : __builtin_nanf("");
+#endif
+#if VAD_HOP_DENOISE
+    // -- a window of the noise class: the raw row of its middle frame (three
+    // hops old, slot (c + 2) % 5 of the spectrum ring) joins the noise rows,
+    // and the estimate is taken anew; it holds from the next hop on
+    if (have && dn.update && __builtin_amdgcn_readfirstlane((int)label) == dn.noise_class) {
+      const float4 mid = reinterpret_cast<const float4*>(dn_spec + ((c + 2) % 5) * kBins)[ln];
+      dn_e = dn_estimate(dn_push_mean(dn_rows, dn_n, mid, ln), dn.alpha, ln);
+    }
 #endif
     c = ring_count_next(c);
     asm volatile("" ::: "memory");
@@ -283,3 +313,7 @@
     for (int d = 0; d < 5; ++d) rs[d * mfcc_n + lane] = rv[d];
   }
   if (lane == 0) count[s] = c;
+#if VAD_HOP_DENOISE
+  reinterpret_cast<float4*>(dn.est + dn_s * kBins)[lane] = dn_e;
+  if (lane == 0) dn.held[s] = dn_n;
+#endif

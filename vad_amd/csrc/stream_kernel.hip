@@ -14,6 +14,7 @@
 #include "ffn_dev.h"
 #include "score_dev.h"
 #include "stream_hop.h"
+#include "stream_denoise.h"
 
 namespace vad {
 
@@ -169,7 +170,9 @@ __global__ __launch_bounds__(1024) void stream_hop_kernel(const float* __restric
                                                           uint8_t* __restrict__ labels, int n_hops,
                                                           int64_t hop_kstride, int64_t lab_kstride) {
 #define VAD_HOP_SCORE 0
+#define VAD_HOP_DENOISE 0
 #include "stream_hop_ffn_body.inc"
+#undef VAD_HOP_DENOISE
 #undef VAD_HOP_SCORE
 }
 
@@ -181,7 +184,24 @@ __global__ __launch_bounds__(1024) void stream_hop_scores_kernel(
     float* __restrict__ ring, int* __restrict__ count, uint8_t* __restrict__ labels, int n_hops, int64_t hop_kstride,
     int64_t lab_kstride, int active, float* __restrict__ scores, int64_t score_kstride) {
 #define VAD_HOP_SCORE 1
+#define VAD_HOP_DENOISE 0
 #include "stream_hop_ffn_body.inc"
+#undef VAD_HOP_DENOISE
+#undef VAD_HOP_SCORE
+}
+
+// The denoising form (stream_denoise.h): the scored kernel's arguments plus
+// the denoise state; `scores` may be null.
+template <int NR, class TH>
+__global__ __launch_bounds__(1024) void stream_hop_denoise_kernel(
+    const float* __restrict__ blob, int blob_n, int nf, int n_taps, FfnDev net, float* __restrict__ frames,
+    int64_t fstride, int len, const TH* __restrict__ hop, int64_t hstride, int hlen, int64_t n_streams, int mfcc_n,
+    float* __restrict__ ring, int* __restrict__ count, uint8_t* __restrict__ labels, int n_hops, int64_t hop_kstride,
+    int64_t lab_kstride, int active, float* __restrict__ scores, int64_t score_kstride, HopDenoise dn) {
+#define VAD_HOP_SCORE 1
+#define VAD_HOP_DENOISE 1
+#include "stream_hop_ffn_body.inc"
+#undef VAD_HOP_DENOISE
 #undef VAD_HOP_SCORE
 }
 
@@ -210,6 +230,19 @@ static hipError_t launch_stream_hop_scores_t(const float* blob, int blob_n, int 
       hop_kstride, lab_kstride, active, scores, score_kstride);
 }
 
+template <class TH>
+static hipError_t launch_stream_hop_denoise_t(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net,
+                                              float* frames, int64_t fstride, int len, const void* hop,
+                                              int64_t hstride, int hlen, int64_t n_streams, int mfcc_n, float* ring,
+                                              int* count, uint8_t* labels, int n_hops, int64_t hop_kstride,
+                                              int64_t lab_kstride, int active, float* scores, int64_t score_kstride,
+                                              const HopDenoise& dn, hipStream_t st) {
+  return launch_hop_kernels<&stream_hop_denoise_kernel<7, TH>, &stream_hop_denoise_kernel<16, TH>>(
+      (size_t)(blob_n + net.wraw_n) * sizeof(float), len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, net,
+      frames, fstride, len, (const TH*)hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops,
+      hop_kstride, lab_kstride, active, scores, score_kstride, dn);
+}
+
 // hop: fp32 samples (hop_bytes 4) or int16 PCM (2); strides in elements
 hipError_t launch_stream_hop(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net, float* frames,
                              int64_t fstride, int len, const void* hop, int hop_bytes, int64_t hstride, int hlen,
@@ -229,6 +262,78 @@ hipError_t launch_stream_hop_scores(const float* blob, int blob_n, int nf, int n
   const auto launch = hop_bytes == 2 ? launch_stream_hop_scores_t<int16_t> : launch_stream_hop_scores_t<float>;
   return launch(blob, blob_n, nf, n_taps, net, frames, fstride, len, hop, hstride, hlen, n_streams, mfcc_n, ring,
                 count, labels, n_hops, hop_kstride, lab_kstride, active, scores, score_kstride, st);
+}
+
+// the denoising form: scores may be null
+hipError_t launch_stream_hop_denoise(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net,
+                                     float* frames, int64_t fstride, int len, const void* hop, int hop_bytes,
+                                     int64_t hstride, int hlen, int64_t n_streams, int mfcc_n, float* ring, int* count,
+                                     uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride, int active,
+                                     float* scores, int64_t score_kstride, const HopDenoise& dn, hipStream_t st) {
+  const auto launch = hop_bytes == 2 ? launch_stream_hop_denoise_t<int16_t> : launch_stream_hop_denoise_t<float>;
+  return launch(blob, blob_n, nf, n_taps, net, frames, fstride, len, hop, hstride, hlen, n_streams, mfcc_n, ring,
+                count, labels, n_hops, hop_kstride, lab_kstride, active, scores, score_kstride, dn, st);
+}
+
+// ---------------------------------------------------------------------------
+// The noise frames of every stream (load_init_inactive_frames,
+// sklearn_analyser.py:40-44): n frames per stream become the n noise rows, in
+// the order given, and the estimate is taken from them.  One wave per stream;
+// a row is the hop kernels' power spectrum of that frame, bit for bit
+// (dn_frame_power).  No barrier: a wave's LDS is its own.
+// ---------------------------------------------------------------------------
+template <class TH>
+__global__ __launch_bounds__(256) void stream_noise_load_kernel(const float* __restrict__ blob,
+                                                                const TH* __restrict__ fr, int64_t sstride,
+                                                                int64_t fstride, int len, int n, int64_t n_streams,
+                                                                float* __restrict__ rows, int* __restrict__ held,
+                                                                float* __restrict__ est, float alpha) {
+  __shared__ __attribute__((aligned(16))) float sm[4 * 2 * kHopZ];
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int64_t s = (int64_t)blockIdx.x * 4 + wv;
+  if (s >= n_streams) return;
+  float2* z0 = reinterpret_cast<float2*>(sm + wv * 2 * kHopZ);
+  float2* z1 = reinterpret_cast<float2*>(sm + wv * 2 * kHopZ + kHopZ);
+  const float2* tw = reinterpret_cast<const float2*>(blob);
+  const int used = len < kFftN ? len : kFftN;
+  float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int j = 0; j < n; ++j) {
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const TH* x = fr + s * sstride + (int64_t)j * fstride;
+    float* xs = reinterpret_cast<float*>(z1);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int t = ln + 64 * i;
+      xs[2 * zp(t >> 1) + (t & 1)] = t < used ? (float)x[t] : 0.f;
+    }
+    asm volatile("" ::: "memory");
+    dn_frame_power(z0, z1, tw, ln);
+    const float4 p = reinterpret_cast<const float4*>(z0)[ln];
+    reinterpret_cast<float4*>(rows + (s * kNoiseRows + j) * kBins)[ln] = p;
+    sum = j == 0 ? p : make_float4(sum.x + p.x, sum.y + p.y, sum.z + p.z, sum.w + p.w);
+    asm volatile("" ::: "memory");
+  }
+  const float fn = (float)n;
+  const float4 m = make_float4(sum.x / fn, sum.y / fn, sum.z / fn, sum.w / fn);
+  reinterpret_cast<float4*>(est + s * kBins)[lane] = dn_estimate(m, alpha, lane);
+  if (lane == 0) held[s] = n;
+}
+
+// fr: (S, n, len) fp32 (in_bytes 4) or int16 (2); strides in elements
+hipError_t launch_stream_noise_load(const float* blob, const void* fr, int in_bytes, int64_t sstride, int64_t fstride,
+                                    int len, int n, int64_t n_streams, float* rows, int* held, float* est,
+                                    float alpha, hipStream_t st) {
+  if (n_streams <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((n_streams + 3) / 4));
+  if (in_bytes == 2)
+    hipLaunchKernelGGL(stream_noise_load_kernel<int16_t>, grid, dim3(256), 0, st, blob, (const int16_t*)fr, sstride,
+                       fstride, len, n, n_streams, rows, held, est, alpha);
+  else
+    hipLaunchKernelGGL(stream_noise_load_kernel<float>, grid, dim3(256), 0, st, blob, (const float*)fr, sstride,
+                       fstride, len, n, n_streams, rows, held, est, alpha);
+  return hipGetLastError();
 }
 
 }  // namespace vad

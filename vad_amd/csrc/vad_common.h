@@ -177,6 +177,37 @@ hipError_t launch_stream_hop_tree_scores(const float* blob, int blob_n, int nf, 
                                          hipStream_t st);
 hipError_t launch_stream_tree_ring(const TreeNodeC* cnodes, int n_nodes, const float* newrow, float* ring, int* count,
                                    int64_t n_streams, int mfcc_n, uint8_t* labels, hipStream_t st);
+// Live spectral subtraction in the hop kernels (stream_denoise.h): the state
+// of every stream, contiguous, in the kernels' units |2X|^2; all zero = fresh.
+constexpr int kNoiseRows = 5;
+struct HopDenoise {
+  float* spec;      // (S, 5, 256) power rows of the last five frames, slot = the MFCC ring's
+  float* rows;      // (S, 5, 256) noise rows in arrival order, row 0 the oldest
+  int* held;        // (S) rows held, 0..5
+  float* est;       // (S, 256) the noise estimate in force
+  float alpha;      // the low pass's coefficient, in [0, 1)
+  int noise_class;  // the label whose windows feed the noise rows
+  int update;       // 0: the rows and the estimate are frozen
+};
+// the denoising hop kernels: the scored forms' arguments (scores, and the
+// tree's node_score with it, may be null) plus the state
+hipError_t launch_stream_hop_denoise(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net,
+                                     float* frames, int64_t fstride, int len, const void* hop, int hop_bytes,
+                                     int64_t hstride, int hlen, int64_t n_streams, int mfcc_n, float* ring, int* count,
+                                     uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride, int active,
+                                     float* scores, int64_t score_kstride, const HopDenoise& dn, hipStream_t st);
+hipError_t launch_stream_hop_tree_denoise(const float* blob, int blob_n, int nf, int n_taps, const TreeNodeC* cnodes,
+                                          const TreeNode* nodes, int n_nodes, bool force_global, float* frames,
+                                          int64_t fstride, int len, const void* hop, int hop_bytes, int64_t hstride,
+                                          int hlen, int64_t n_streams, int mfcc_n, float* ring, int* count,
+                                          uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
+                                          const float* node_score, float* scores, int64_t score_kstride,
+                                          const HopDenoise& dn, hipStream_t st);
+// n noise frames per stream, (S, n, len) fp32 / int16 (in_bytes 4 / 2), into
+// the noise rows, the count and the estimate
+hipError_t launch_stream_noise_load(const float* blob, const void* fr, int in_bytes, int64_t sstride, int64_t fstride,
+                                    int len, int n, int64_t n_streams, float* rows, int* held, float* est,
+                                    float alpha, hipStream_t st);
 hipError_t launch_preemphasis(const float* x, float* y, int64_t n_rows, int64_t row_len, int64_t stride, float a,
                               hipStream_t st);
 // Streaming segments (stream_segments_kernel.hip): n_hops hops of every

@@ -59,6 +59,22 @@ host forms (step_host, HostPipeline) copy labels only: the scores stay on the
 device, in ``score_block``, valid once the step has run.  segmenter(on=...,
 off=..., pad=...) feeds them to the online segmenter.
 
+Noise subtraction: StreamBatch(..., denoise=True, alpha=0.9, noise_class=0,
+noise_update=True) makes the reference's dead spectral subtraction live
+(sklearn_analyser.py:84-101 computes it, :122-123 drops it): per stream the
+hop kernel keeps the power rows of the last five frames (``spec_ring``), up
+to five noise rows in arrival order (``noise_rows``, ``noise_count``) and the
+noise estimate (``noise_estimate``: the rows' mean, low-passed over the bins
+with coefficient ``alpha``); a hop's MFCC row is taken from max(p - e, 0), and
+a window labelled ``noise_class`` pushes the raw power row of its middle frame
+into the noise rows (noise_update=False freezes them).  load_noise(frames)
+is load_init_inactive_frames.  Every form of a hop step works as before
+(vad_stream_hops_denoise and its _i16 / tree forms: still one kernel);
+kernel="three" has no denoising.  All four are reported in the reference's
+units |X/512|^2 (the kernels keep |2X|^2: an exact factor 2^-20).  Not covered:
+the clip kernels (the loop is sequential in the frames), SKLearnAnalyzer,
+SimpleStreamBatch.
+
 Blocks in flight: host_pipeline(depth) returns a HostPipeline with `depth`
 slots, each with pinned host buffers and a device input / label block of its
 own, and three streams (copy-in, compute, copy-out): submit(d) enqueues slot
@@ -114,7 +130,8 @@ class StreamBatch:
     "global" always walks from global memory (same labels)."""
 
     def __init__(self, n_streams, ffn, cfg: MfccConfig = MfccConfig(), device=None, kernel="hop",
-                 hops_per_step=1, input_dtype=torch.float32, tree_walk="auto", scores=False, active=1):
+                 hops_per_step=1, input_dtype=torch.float32, tree_walk="auto", scores=False, active=1,
+                 denoise=False, alpha=0.9, noise_class=0, noise_update=True):
         if input_dtype not in (torch.float32, torch.int16):
             raise ValueError("input_dtype must be torch.float32 or torch.int16")
         if tree_walk not in _TREE_WALKS:
@@ -140,6 +157,19 @@ class StreamBatch:
             n_cls = ffn.score_classes() if self.is_tree else int(ffn.layers[-1][1].shape[0])
             if not 0 <= self.active < n_cls:
                 raise ValueError(f"active must be a class index below {n_cls}, got {active}")
+        self.denoise = bool(denoise)
+        if self.denoise:
+            if kernel == "three":
+                raise ValueError("noise subtraction lives in the one-kernel hop: kernel='three' has none")
+            if cfg.fft_n != 512:
+                raise ValueError("noise subtraction needs fft_n = 512 (the hop kernel's FFT)")
+            self.alpha, self.noise_class, self.noise_update = float(alpha), int(noise_class), bool(noise_update)
+            if not 0.0 <= self.alpha < 1.0:  # false for NaN
+                raise ValueError(f"alpha must be in [0, 1), got {alpha}")
+            n_cls = 1 + max(int(c) for c, f in zip(ffn.leaf, ffn.feature) if f < 0) if self.is_tree \
+                else int(ffn.layers[-1][1].shape[0])  # the tree's classes: those of its leaves
+            if not 0 <= self.noise_class < n_cls:
+                raise ValueError(f"noise_class must be a class index below {n_cls}, got {noise_class}")
         self.cfg, self.ffn, self.n, self.kernel = cfg, ffn, int(n_streams), kernel
         self.classifier = ffn
         self.plan = MfccPlan.from_config(cfg)
@@ -163,10 +193,56 @@ class StreamBatch:
         self.labels = self.label_block[K - 1]
         self.score_block = torch.full((K, S), float("nan"), dtype=torch.float32, device=dev) if self.scores else None
         self.scratch = torch.zeros((S, C), dtype=torch.float32, device=dev)
+        if self.denoise:  # the kernels' units |2X|^2; the properties below scale them
+            self._spec = torch.zeros((S, 5, 256), dtype=torch.float32, device=dev)
+            self._noise = torch.zeros((S, 5, 256), dtype=torch.float32, device=dev)
+            self._est = torch.zeros((S, 256), dtype=torch.float32, device=dev)
+            self.noise_count = torch.zeros((S,), dtype=torch.int32, device=dev)
         self.graph = None
         self.graph_host_io = False
         self.host_inputs = None
         self.host_labels = None
+
+    _UNITS = 2.0 ** -20  # |2X|^2 -> |X/512|^2, exact
+
+    def _need_denoise(self):
+        if not self.denoise:
+            raise ValueError("build the batch with denoise=True")
+
+    @property
+    def spec_ring(self):
+        """(S, 5, 256) power rows |X/512|^2 of the last five frames; slot as ``ring``."""
+        self._need_denoise()
+        return self._spec * self._UNITS
+
+    @property
+    def noise_rows(self):
+        """(S, 5, 256) noise rows in arrival order; the first noise_count[s] of stream s are held."""
+        self._need_denoise()
+        return self._noise * self._UNITS
+
+    @property
+    def noise_estimate(self):
+        """(S, 256) the estimate the next hop subtracts."""
+        self._need_denoise()
+        return self._est * self._UNITS
+
+    def load_noise(self, frames):
+        """frames (S, n, frame_size), n = 1..5, a CUDA tensor of the batch's
+        input dtype: their power rows become the noise rows, in order, and
+        the estimate is taken from them (load_init_inactive_frames)."""
+        self._need_denoise()
+        if frames.dim() != 3 or frames.shape[0] != self.n or not 1 <= frames.shape[1] <= 5 \
+                or frames.shape[2] != self.cfg.frame_size or frames.dtype != self.input_dtype or not frames.is_cuda:
+            raise ValueError(f"frames must be a CUDA {self._dtype_name} tensor of shape "
+                             f"({self.n}, 1..5, {self.cfg.frame_size})")
+        if frames.stride(2) != 1:
+            frames = frames.contiguous()
+        name = "vad_stream_noise_load_i16" if self._i16 else "vad_stream_noise_load"
+        _lib.check(getattr(_lib.lib(), name)(
+            self.plan.handle, ctypes.c_void_p(frames.data_ptr()), frames.stride(0), frames.stride(1),
+            self.cfg.frame_size, frames.shape[1], self.n, _lib.ptr(self._noise), _lib.ptr(self.noise_count),
+            _lib.ptr(self._est), self.alpha, _lib.stream_ptr()), name)
 
     def prime(self, carry):
         """Set the last frame_size - hop samples of every stream (S, L-H),
@@ -181,6 +257,9 @@ class StreamBatch:
         self.label_block.fill_(255)
         if self.scores:
             self.score_block.fill_(float("nan"))
+        if self.denoise:
+            for t in (self._spec, self._noise, self._est, self.noise_count):
+                t.zero_()
 
     def _hop_call(self, h, n_hops=1, labels=None, stream=None):
         """vad_stream_hops (_i16 for an int16 batch) with the per-batch
@@ -191,11 +270,15 @@ class StreamBatch:
         if getattr(self, "_hop_head", None) is None:
             L = self.cfg.frame_size
             self._hop_name = ("vad_stream_hops_tree" if self.is_tree else "vad_stream_hops") + \
-                ("_scores" if self.scores else "") + ("_i16" if self._i16 else "")
+                ("_denoise" if self.denoise else "_scores" if self.scores else "") + ("_i16" if self._i16 else "")
             if self.scores and self.is_tree:
                 self.ffn.plan_with_scores()
             # rows [0, n_hops) of score_block, whichever label rows the call writes
             self._hop_scores = (self.active, _lib.ptr(self.score_block), self.n) if self.scores else ()
+            if self.denoise:  # the scored entry's arguments (scores may be null), then the state and the options
+                self._hop_scores = (self._hop_scores or (0, None, 0)) + (
+                    _lib.ptr(self._spec), _lib.ptr(self._noise), _lib.ptr(self.noise_count), _lib.ptr(self._est),
+                    self.alpha, self.noise_class, int(self.noise_update))
             self._hop_fn = getattr(_lib.lib(), self._hop_name)
             self._hop_head = (self.plan.handle, self.ffn.plan.handle, _lib.ptr(self.frames), L, L)
             self._hop_mid = (_lib.ptr(self.ring), _lib.ptr(self.count))
@@ -329,6 +412,8 @@ class StreamBatch:
         s.wait_stream(torch.cuda.current_stream())
         saved = (self.frames.clone(), self.ring.clone(), self.count.clone(), self.label_block.clone())
         saved_scores = self.score_block.clone() if self.scores else None
+        dn_state = (self._spec, self._noise, self._est, self.noise_count) if self.denoise else ()
+        dn_saved = [t.clone() for t in dn_state]
         if host_io:
             self.attach_host_io()
             body = self._host_body
@@ -342,6 +427,8 @@ class StreamBatch:
         self.count.copy_(saved[2]); self.label_block.copy_(saved[3])
         if self.scores:
             self.score_block.copy_(saved_scores)
+        for t, v in zip(dn_state, dn_saved):
+            t.copy_(v)
         # keep_graph: the captured hipGraph_t stays alive beside its exec, so
         # the replay plan can read its nodes (vad_graph_plan_create: a
         # one-kernel-node graph -- the one-hop step -- is dispatched as its
