@@ -745,6 +745,67 @@ int vad_stream_noise_load(const vad_mfcc_plan* plan, const float* frames, int64_
 int vad_stream_noise_load_i16(const vad_mfcc_plan* plan, const int16_t* frames, int64_t stream_stride,
                               int64_t frame_stride, int32_t frame_len, int32_t n, int64_t n_streams,
                               float* noise_rows, int32_t* noise_count, float* noise_est, float alpha, void* stream);
+/* Sessions: streams that join, leave and stall inside the hop kernel.  The
+ * entries above advance every stream by n_hops hops; these read, per stream
+ * and launch, two more device arrays (a stream is one wave, so both are scalar
+ * in it):
+ *   hop_counts (S) int32   the hops stream s takes in this launch,
+ *                          n_s = min(max(hop_counts[s], 0), n_hops): rows
+ *                          0..n_s-1 of its column of the hop block; rows from
+ *                          n_s on are not read
+ *   restart    (S) uint8   nonzero: before its hops the stream's state becomes
+ *                          a fresh stream's -- frame, ring and count zero, and
+ *                          with denoising its spec_ring, noise_rows,
+ *                          noise_count and noise_est too; the kernel then
+ *                          stores restart[s] = 0 (the flag is consumed: set it
+ *                          once, a graph replay does not restart again)
+ * The stream then advances n_s hops exactly as by the entries above: label
+ * and score rows 0..n_s-1 hold what they write (255 / NaN during the first
+ * five hops after a restart), rows n_s..n_hops-1 hold VAD_LABEL_NO_HOP and NaN.
+ * With n_s = 0 and no restart no byte of the stream's state is written.  With
+ * all counts n_hops and no restart, labels, scores and state are those of the
+ * entries above, bit for bit.
+ * Arguments: those of the denoising entry of the same classifier and input
+ * type -- scores may be null; the four state arrays are either all set, or
+ * all null for no denoising (alpha, noise_class and update are then not read)
+ * -- then hop_counts and restart.  Row 0 of every stream's column of the hop
+ * block is loaded whatever its count (and dropped), so the whole block must be
+ * readable, as for the entries above.
+ * Refusals (VAD_EINVAL, before any device call): a null hop_counts or restart;
+ * a partly set denoise state; everything the denoising entries refuse (without
+ * denoising: everything the scored entries refuse, a null `scores` excepted). */
+#define VAD_LABEL_NO_HOP 254 /* a label row the stream has no hop in */
+int vad_stream_hops_sessions(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
+                             int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len,
+                             int64_t n_streams, int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count,
+                             uint8_t* labels, int64_t label_block_stride, int32_t active, float* scores,
+                             int64_t score_block_stride, float* spec_ring, float* noise_rows, int32_t* noise_count,
+                             float* noise_est, float alpha, int32_t noise_class, int32_t update,
+                             const int32_t* hop_counts, uint8_t* restart, void* stream);
+int vad_stream_hops_sessions_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames,
+                                 int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                                 int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                 float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                                 int32_t active, float* scores, int64_t score_block_stride, float* spec_ring,
+                                 float* noise_rows, int32_t* noise_count, float* noise_est, float alpha,
+                                 int32_t noise_class, int32_t update, const int32_t* hop_counts, uint8_t* restart,
+                                 void* stream);
+int vad_stream_hops_tree_sessions(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                                  int64_t frame_stride, int32_t frame_len, const float* hop, int64_t hop_stride,
+                                  int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                  float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                                  int32_t walk, int32_t active, float* scores, int64_t score_block_stride,
+                                  float* spec_ring, float* noise_rows, int32_t* noise_count, float* noise_est,
+                                  float alpha, int32_t noise_class, int32_t update, const int32_t* hop_counts,
+                                  uint8_t* restart, void* stream);
+int vad_stream_hops_tree_sessions_i16(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+                                      int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                                      int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                                      float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                                      int32_t walk, int32_t active, float* scores, int64_t score_block_stride,
+                                      float* spec_ring, float* noise_rows, int32_t* noise_count, float* noise_est,
+                                      float alpha, int32_t noise_class, int32_t update, const int32_t* hop_counts,
+                                      uint8_t* restart, void* stream);
 /* Replay a captured hipGraph (hipGraphExec_t) on `stream`: the per-hop step
  * of a StreamBatch captured with its host I/O (the H2D copy of every
  * stream's new samples from pinned memory, the hop kernel, the D2H copy of

@@ -26,6 +26,7 @@ FFN_EXACT_F32 = 0
 FFN_SPLIT_F16 = 1
 TREE_WALK_AUTO = 0
 TREE_WALK_GLOBAL = 1
+LABEL_NO_HOP = 254
 CSV_TILE = 4096
 CSV_CARRY_PASS = 256
 CSV_MAX_LINE = 4096
@@ -136,6 +137,15 @@ SIGNATURES = {
     **{"vad_stream_hops_tree_denoise" + t: (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32,
                                                     c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp,
                                                     c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp])
+       for t in ("", "_i16")},
+    # the denoising entries' arguments (the state all null: no denoising), then hop_counts, restart
+    **{"vad_stream_hops_sessions" + t: (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32,
+                                                c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                                c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp])
+       for t in ("", "_i16")},
+    **{"vad_stream_hops_tree_sessions" + t: (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32,
+                                                     c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp,
+                                                     c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp])
        for t in ("", "_i16")},
     **{"vad_stream_noise_load" + t: (c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_f32,
                                              c_vp])

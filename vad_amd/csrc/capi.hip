@@ -1417,7 +1417,8 @@ static int stream_hops_denoise_entry(const vad_mfcc_plan* plan, const vad_ffn_pl
                                      uint8_t* labels, int64_t label_block_stride, int32_t walk, int32_t active,
                                      float* scores, int64_t score_block_stride, float* spec_ring, float* noise_rows,
                                      int32_t* noise_count, float* noise_est, float alpha, int32_t noise_class,
-                                     int32_t update, void* stream) {
+                                     int32_t update, void* stream, bool sessions = false,
+                                     const int32_t* hop_counts = nullptr, uint8_t* restart = nullptr) {
   if (!plan || (!ffn && !tree) || n_streams < 0 || n_hops < 0 || frame_len <= 0 || frame_len > 1024 || hop_len <= 0 ||
       hop_len > frame_len || frame_stride < frame_len || hop_stride < hop_len)
     return VAD_EINVAL;
@@ -1426,20 +1427,39 @@ static int stream_hops_denoise_entry(const vad_mfcc_plan* plan, const vad_ffn_pl
   if (scores && n_hops > 1 && score_block_stride < n_streams) return VAD_EINVAL;
   if (n_hops > 1 && !vad_hop_layout_disjoint(n_streams, n_hops, hop_block_stride, hop_stride, hop_len))
     return VAD_EINVAL;
-  if (!denoise_alpha_ok(alpha) || (update != 0 && update != 1) || noise_class < 0) return VAD_EINVAL;
-  if (!denoise_state_ok(n_streams, true, spec_ring, noise_rows, noise_count, noise_est)) return VAD_EINVAL;
+  // the sessions entries run without denoising when all four state arrays are null (alpha, noise_class and
+  // update are then not read); a partly set state is refused like any null array
+  const bool denoise = !sessions || spec_ring || noise_rows || noise_count || noise_est;
+  if (denoise) {
+    if (!denoise_alpha_ok(alpha) || (update != 0 && update != 1) || noise_class < 0) return VAD_EINVAL;
+    if (!denoise_state_ok(n_streams, true, spec_ring, noise_rows, noise_count, noise_est)) return VAD_EINVAL;
+  }
+  if (sessions && (!hop_counts || !restart)) return VAD_EINVAL;
   // from here on the plans are read
   if (scores) {
     if (tree && !tree->score_dev) return VAD_EINVAL;  // vad_tree_plan_set_scores first
     if (active < 0 || active >= (tree ? tree->n_score_classes : ffn->net.n_classes)) return VAD_EINVAL;
   }
-  if (noise_class >= (tree ? tree->n_classes : ffn->net.n_classes)) return VAD_EINVAL;
+  if (denoise && noise_class >= (tree ? tree->n_classes : ffn->net.n_classes)) return VAD_EINVAL;
   if (n_streams == 0 || n_hops == 0) return VAD_OK;
   if (!frames || !hop || !ring || !count || !labels) return VAD_EINVAL;
   if ((tree ? tree->n_features : ffn->net.dims[0]) > 3 * plan->host.mfcc_n) return VAD_EINVAL;
   if (plan->generic()) return VAD_EUNSUPPORTED;  // its FFT is the 256-point Stockham of fft_n = 512
   if (plan->spec == kSpecWindow) return VAD_EUNSUPPORTED;  // its table blob carries no analysis window
   const HopDenoise dn = {spec_ring, noise_rows, noise_count, noise_est, alpha, noise_class, update};
+  if (sessions && tree)
+    return (int)launch_stream_hop_tree_sessions(
+        plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps, tree->cnodes_dev, tree->nodes_dev,
+        tree->n_nodes, walk == VAD_TREE_WALK_GLOBAL, frames, frame_stride, frame_len, hop, hop_bytes, hop_stride,
+        hop_len, n_streams, plan->host.mfcc_n, ring, count, labels, n_hops, hop_block_stride, label_block_stride,
+        scores ? tree->score_dev + (size_t)active * (size_t)tree->n_nodes : nullptr, scores, score_block_stride,
+        denoise ? &dn : nullptr, hop_counts, restart, (hipStream_t)stream);
+  if (sessions)
+    return (int)launch_stream_hop_sessions(plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps,
+                                           ffn->net, frames, frame_stride, frame_len, hop, hop_bytes, hop_stride,
+                                           hop_len, n_streams, plan->host.mfcc_n, ring, count, labels, n_hops,
+                                           hop_block_stride, label_block_stride, active, scores, score_block_stride,
+                                           denoise ? &dn : nullptr, hop_counts, restart, (hipStream_t)stream);
   if (tree)
     return (int)launch_stream_hop_tree_denoise(
         plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps, tree->cnodes_dev, tree->nodes_dev,
@@ -1507,6 +1527,64 @@ int vad_stream_hops_tree_denoise_i16(const vad_mfcc_plan* plan, const vad_tree_p
                                    n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk,
                                    active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
                                    alpha, noise_class, update, stream);
+}
+
+// The sessions entries: the denoising entries' arguments (the four state
+// arrays all null for no denoising), then the per-stream hop counts and
+// restart flags.
+int vad_stream_hops_sessions(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames, int64_t frame_stride,
+    int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,
+    int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+    int32_t active, float* scores, int64_t score_block_stride, float* spec_ring, float* noise_rows,
+    int32_t* noise_count, float* noise_est, float alpha, int32_t noise_class, int32_t update,
+    const int32_t* hop_counts, uint8_t* restart, void* stream) {
+  if (!ffn) return VAD_EINVAL;
+  return stream_hops_denoise_entry(plan, ffn, nullptr, frames, frame_stride, frame_len, hop, 4, hop_stride, hop_len,
+                                   n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, 0,
+                                   active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
+                                   alpha, noise_class, update, stream, true, hop_counts, restart);
+}
+
+int vad_stream_hops_sessions_i16(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, float* frames,
+    int64_t frame_stride,
+    int32_t frame_len, const int16_t* hop, int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,
+    int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+    int32_t active, float* scores, int64_t score_block_stride, float* spec_ring, float* noise_rows,
+    int32_t* noise_count, float* noise_est, float alpha, int32_t noise_class, int32_t update,
+    const int32_t* hop_counts, uint8_t* restart, void* stream) {
+  if (!ffn) return VAD_EINVAL;
+  return stream_hops_denoise_entry(plan, ffn, nullptr, frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len,
+                                   n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, 0,
+                                   active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
+                                   alpha, noise_class, update, stream, true, hop_counts, restart);
+}
+
+int vad_stream_hops_tree_sessions(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+    int64_t frame_stride,
+    int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,
+    int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride, int32_t walk,
+    int32_t active, float* scores, int64_t score_block_stride, float* spec_ring, float* noise_rows,
+    int32_t* noise_count, float* noise_est, float alpha, int32_t noise_class, int32_t update,
+    const int32_t* hop_counts, uint8_t* restart, void* stream) {
+  if (!tree) return VAD_EINVAL;
+  return stream_hops_denoise_entry(plan, nullptr, tree, frames, frame_stride, frame_len, hop, 4, hop_stride, hop_len,
+                                   n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk,
+                                   active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
+                                   alpha, noise_class, update, stream, true, hop_counts, restart);
+}
+
+int vad_stream_hops_tree_sessions_i16(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
+    int64_t frame_stride,
+    int32_t frame_len, const int16_t* hop, int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,
+    int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride, int32_t walk,
+    int32_t active, float* scores, int64_t score_block_stride, float* spec_ring, float* noise_rows,
+    int32_t* noise_count, float* noise_est, float alpha, int32_t noise_class, int32_t update,
+    const int32_t* hop_counts, uint8_t* restart, void* stream) {
+  if (!tree) return VAD_EINVAL;
+  return stream_hops_denoise_entry(plan, nullptr, tree, frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len,
+                                   n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk,
+                                   active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
+                                   alpha, noise_class, update, stream, true, hop_counts, restart);
 }
 
 // n frames per stream, (S, n, frame_len) with the strides given in elements,

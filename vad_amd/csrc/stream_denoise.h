@@ -45,6 +45,19 @@ __device__ __forceinline__ void dn_store_subtract(float* pw, int ln, float* spec
   *p4 = d;
 }
 
+// A stream starting over (the sessions kernels' restart): zeros to the lane's
+// own 16 B of the eleven rows -- five of the spectrum ring, five noise rows,
+// the estimate.  The lane alone reads these bytes later in the launch, so no
+// fence follows.
+__device__ __forceinline__ void dn_clear(float* spec, float* rows, float* est, int lane) {
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int j = 0; j < 5; ++j) reinterpret_cast<float4*>(spec + j * kBins)[lane] = z;
+#pragma unroll
+  for (int j = 0; j < kNoiseRows; ++j) reinterpret_cast<float4*>(rows + j * kBins)[lane] = z;
+  reinterpret_cast<float4*>(est)[lane] = z;
+}
+
 // The push: the lane's four bins `nw` of a raw power row go behind the rows
 // held (the oldest row dropped and the others moved down when five are
 // held).  Returns the lane's bins of the mean (((r0 + r1) + r2) + ...) / n in

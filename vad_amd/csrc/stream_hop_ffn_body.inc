@@ -11,6 +11,11 @@
 // noise estimate comes off the power spectrum before the mel bank, and the
 // windows of the noise class feed it (stream_denoise.h); its `scores` may be
 // null.  With VAD_HOP_DENOISE 0 the text is what it was without it.
+// stream_hop_sessions_kernel and stream_hop_sessions_denoise_kernel are the
+// scored form (nullable `scores`) with VAD_HOP_SESSIONS 1, with VAD_HOP_DENOISE
+// 0 and 1: per stream a hop count for this launch and a restart flag, both
+// scalar in the stream's wave (DESIGN.md section 4).  With VAD_HOP_SESSIONS 0
+// the text is what it was without it.
   extern __shared__ __attribute__((aligned(16))) float hsm[];
   const int waves = blockDim.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -77,6 +82,14 @@
   float4* dn_est = reinterpret_cast<float4*>(dn.est + dn_s * kBins);
   int dn_n = __builtin_amdgcn_readfirstlane(dn.held[sc]);
 #endif
+#if VAD_HOP_SESSIONS
+  // the stream's session for this launch, both wave-uniform (scalar): the
+  // hops it takes from its column of the block, min(max(hop_counts[s], 0),
+  // n_hops), and whether it starts over first
+  int n_s = __builtin_amdgcn_readfirstlane(hop_counts[sc]);
+  n_s = n_s < 0 ? 0 : n_s > n_hops ? n_hops : n_s;
+  const int restarted = __builtin_amdgcn_readfirstlane((int)restart[sc]);
+#endif
   // this lane's FFT twiddles (W512^k table = the blob's first 256 complex):
   // stage st's radix-4 butterfly multiplies by W256^(j m), m = (lane mod
   // 4^st) 64 / 4^st, j = 1..3; the real-FFT split by W512^(lane + 64 q)
@@ -112,10 +125,34 @@
   float* act_b = act_a + 64;
   float* fb = scr;  // the frame shift goes through the FFT buffers (2 kHopZ >= 1024 floats)
   const int used = len < kFftN ? len : kFftN;
+#if VAD_HOP_SESSIONS
+  if (restarted) {  // what reset() leaves: the registers here, written back below; the flag is consumed
+#pragma unroll
+    for (int i = 0; i < NR; ++i) v[i] = 0.f;
+#pragma unroll
+    for (int d = 0; d < 5; ++d) rv[d] = 0.f;
+    c = 0;
+#if VAD_HOP_DENOISE
+    dn_clear(dn_spec, dn_rows, dn.est + dn_s * kBins, lane);  // the lane's own 16 B of the eleven rows
+    dn_n = 0;
+#endif
+    if (lane == 0) restart[s] = 0;
+  }
+  if (lane == 0) {  // the rows this stream has no hop in
+    for (int k = n_s; k < n_hops; ++k) {
+      labels[(int64_t)k * lab_kstride + s] = (uint8_t)VAD_LABEL_NO_HOP;
+      if (scores) scores[(int64_t)k * score_kstride + s] = __builtin_nanf("");
+    }
+  }
+  if (n_s == 0 && !restarted) return;  // no hop, no change: nothing is written back
+#define VAD_HOP_N n_s
+#else
+#define VAD_HOP_N n_hops
+#endif
 
   // K hops of this stream back to back: the same computation per hop as K
   // launches of one hop (state carried in registers), the tables staged once
-  for (int k = 0; k < n_hops; ++k) {
+  for (int k = 0; k < VAD_HOP_N; ++k) {
     // the lane index, opaque per hop: otherwise the compiler hoists every
     // lane-dependent LDS address of the hop out of the loop and runs out of
     // registers holding them
@@ -135,7 +172,7 @@
       v[i] = t < keep ? fb[t + hlen] : hn[i];
     }
     asm volatile("" ::: "memory");
-    if (k + 1 < n_hops) {  // the next hop's samples, in flight during this one
+    if (k + 1 < VAD_HOP_N) {  // the next hop's samples, in flight during this one
       const TH* hs = hop + (int64_t)(k + 1) * hop_kstride + s * hstride;
 #pragma unroll
       for (int i = 0; i < NR; ++i) {
@@ -311,7 +348,7 @@
                         hin[3 < net.n_classes ? 3 : 0]};
       label = (uint8_t)argmax_classes(zl, net.n_classes);
 #if VAD_HOP_SCORE
-#if VAD_HOP_DENOISE
+#if VAD_HOP_DENOISE || VAD_HOP_SESSIONS
       if (ln == 0 && scores) {  // the denoising kernel is the scored form; its scores may be null
 #else
       if (ln == 0) {
@@ -322,7 +359,7 @@
                                                  : nc == 4 ? softmax_score<4>(zl, active)
                                                            : softmax_score<1>(zl, active);
       }
-#if VAD_HOP_DENOISE
+#if VAD_HOP_DENOISE || VAD_HOP_SESSIONS
     } else if (ln == 0 && scores) {
 #else
     } else if (ln == 0) {
@@ -357,3 +394,4 @@
 #if VAD_HOP_DENOISE
   if (lane == 0) dn.held[s] = dn_n;
 #endif
+#undef VAD_HOP_N

@@ -14,6 +14,10 @@
 // stream_hop_tree_denoise_kernel is the scored form with VAD_HOP_DENOISE 1
 // (stream_hop_ffn_body.inc says what that adds; `scores`, and with it
 // node_score, may be null).  With VAD_HOP_DENOISE 0 the text is unchanged.
+// stream_hop_tree_sessions_kernel and stream_hop_tree_sessions_denoise_kernel
+// are the scored form (nullable `scores`) with VAD_HOP_SESSIONS 1: the per-stream
+// hop count and restart of stream_hop_ffn_body.inc.  With VAD_HOP_SESSIONS 0 the
+// text is unchanged.
   extern __shared__ __attribute__((aligned(16))) float hsm[];
   const int waves = blockDim.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -71,6 +75,14 @@
   float4 dn_e = reinterpret_cast<const float4*>(dn.est + dn_s * kBins)[lane];
   int dn_n = __builtin_amdgcn_readfirstlane(dn.held[sc]);
 #endif
+#if VAD_HOP_SESSIONS
+  // the stream's session for this launch, both wave-uniform (scalar): the
+  // hops it takes from its column of the block, min(max(hop_counts[s], 0),
+  // n_hops), and whether it starts over first
+  int n_s = __builtin_amdgcn_readfirstlane(hop_counts[sc]);
+  n_s = n_s < 0 ? 0 : n_s > n_hops ? n_hops : n_s;
+  const int restarted = __builtin_amdgcn_readfirstlane((int)restart[sc]);
+#endif
   // this lane's FFT twiddles (stream_hop_kernel: registers in the 7-chunk
   // build, the staged table in the 16-chunk one)
   const float2* tw_g = reinterpret_cast<const float2*>(blob);
@@ -100,8 +112,33 @@
   float* act_a = lmr + kMaxFilters;
   float* fb = scr;  // the frame shift goes through the FFT buffers (2 kHopZ >= 1024 floats)
   const int used = len < kFftN ? len : kFftN;
+#if VAD_HOP_SESSIONS
+  if (restarted) {  // what reset() leaves: the registers here, written back below; the flag is consumed
+#pragma unroll
+    for (int i = 0; i < NR; ++i) v[i] = 0.f;
+#pragma unroll
+    for (int d = 0; d < 5; ++d) rv[d] = 0.f;
+    c = 0;
+#if VAD_HOP_DENOISE
+    dn_clear(dn_spec, dn_rows, dn.est + dn_s * kBins, lane);  // the lane's own 16 B of the eleven rows
+    dn_e = make_float4(0.f, 0.f, 0.f, 0.f);
+    dn_n = 0;
+#endif
+    if (lane == 0) restart[s] = 0;
+  }
+  if (lane == 0) {  // the rows this stream has no hop in
+    for (int k = n_s; k < n_hops; ++k) {
+      labels[(int64_t)k * lab_kstride + s] = (uint8_t)VAD_LABEL_NO_HOP;
+      if (scores) scores[(int64_t)k * score_kstride + s] = __builtin_nanf("");
+    }
+  }
+  if (n_s == 0 && !restarted) return;  // no hop, no change: nothing is written back
+#define VAD_HOP_N n_s
+#else
+#define VAD_HOP_N n_hops
+#endif
 
-  for (int k = 0; k < n_hops; ++k) {
+  for (int k = 0; k < VAD_HOP_N; ++k) {
     // the lane index, opaque per hop (stream_hop_kernel: keeps the hop's LDS
     // addresses out of registers across hops)
     int ln = lane;
@@ -119,7 +156,7 @@
       v[i] = t < keep ? fb[t + hlen] : hn[i];
     }
     asm volatile("" ::: "memory");
-    if (k + 1 < n_hops) {  // the next hop's samples, in flight during this one
+    if (k + 1 < VAD_HOP_N) {  // the next hop's samples, in flight during this one
       const TH* hs = hop + (int64_t)(k + 1) * hop_kstride + s * hstride;
 #pragma unroll
       for (int i = 0; i < NR; ++i) {
@@ -285,7 +322,7 @@
       }
     }
     if (ln == 0) lab_k[s] = (uint8_t)label;
-#if VAD_HOP_DENOISE
+#if VAD_HOP_DENOISE || VAD_HOP_SESSIONS
     if (ln == 0 && scores) scores[(int64_t)k * score_kstride + s] = have ? node_score[leaf] : __builtin_nanf("");
 #elif VAD_HOP_SCORE
     if (ln == 0) scores[(int64_t)k * score_kstride + s] = have ? node_score[leaf] : __builtin_nanf("");
@@ -317,3 +354,4 @@
   reinterpret_cast<float4*>(dn.est + dn_s * kBins)[lane] = dn_e;
   if (lane == 0) dn.held[s] = dn_n;
 #endif
+#undef VAD_HOP_N

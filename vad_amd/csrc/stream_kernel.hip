@@ -171,7 +171,9 @@ __global__ __launch_bounds__(1024) void stream_hop_kernel(const float* __restric
                                                           int64_t hop_kstride, int64_t lab_kstride) {
 #define VAD_HOP_SCORE 0
 #define VAD_HOP_DENOISE 0
+#define VAD_HOP_SESSIONS 0
 #include "stream_hop_ffn_body.inc"
+#undef VAD_HOP_SESSIONS
 #undef VAD_HOP_DENOISE
 #undef VAD_HOP_SCORE
 }
@@ -185,7 +187,9 @@ __global__ __launch_bounds__(1024) void stream_hop_scores_kernel(
     int64_t lab_kstride, int active, float* __restrict__ scores, int64_t score_kstride) {
 #define VAD_HOP_SCORE 1
 #define VAD_HOP_DENOISE 0
+#define VAD_HOP_SESSIONS 0
 #include "stream_hop_ffn_body.inc"
+#undef VAD_HOP_SESSIONS
 #undef VAD_HOP_DENOISE
 #undef VAD_HOP_SCORE
 }
@@ -200,9 +204,68 @@ __global__ __launch_bounds__(1024) void stream_hop_denoise_kernel(
     int64_t lab_kstride, int active, float* __restrict__ scores, int64_t score_kstride, HopDenoise dn) {
 #define VAD_HOP_SCORE 1
 #define VAD_HOP_DENOISE 1
+#define VAD_HOP_SESSIONS 0
 #include "stream_hop_ffn_body.inc"
+#undef VAD_HOP_SESSIONS
 #undef VAD_HOP_DENOISE
 #undef VAD_HOP_SCORE
+}
+
+// The sessions forms: the scored kernel (scores may be null), without and
+// with the denoise state, plus per stream the hops it takes in this launch
+// (hop_counts, clamped to 0..n_hops) and a restart flag the kernel consumes.
+// Rows n_s..n_hops-1 of a stream's labels hold VAD_LABEL_NO_HOP, of its scores
+// NaN; a stream with no hop and no restart writes nothing else.
+template <int NR, class TH>
+__global__ __launch_bounds__(1024) void stream_hop_sessions_kernel(
+    const float* __restrict__ blob, int blob_n, int nf, int n_taps, FfnDev net, float* __restrict__ frames,
+    int64_t fstride, int len, const TH* __restrict__ hop, int64_t hstride, int hlen, int64_t n_streams, int mfcc_n,
+    float* __restrict__ ring, int* __restrict__ count, uint8_t* __restrict__ labels, int n_hops, int64_t hop_kstride,
+    int64_t lab_kstride, int active, float* __restrict__ scores, int64_t score_kstride,
+    const int* __restrict__ hop_counts, uint8_t* __restrict__ restart) {
+#define VAD_HOP_SCORE 1
+#define VAD_HOP_DENOISE 0
+#define VAD_HOP_SESSIONS 1
+#include "stream_hop_ffn_body.inc"
+#undef VAD_HOP_SESSIONS
+#undef VAD_HOP_DENOISE
+#undef VAD_HOP_SCORE
+}
+
+template <int NR, class TH>
+__global__ __launch_bounds__(1024) void stream_hop_sessions_denoise_kernel(
+    const float* __restrict__ blob, int blob_n, int nf, int n_taps, FfnDev net, float* __restrict__ frames,
+    int64_t fstride, int len, const TH* __restrict__ hop, int64_t hstride, int hlen, int64_t n_streams, int mfcc_n,
+    float* __restrict__ ring, int* __restrict__ count, uint8_t* __restrict__ labels, int n_hops, int64_t hop_kstride,
+    int64_t lab_kstride, int active, float* __restrict__ scores, int64_t score_kstride, HopDenoise dn,
+    const int* __restrict__ hop_counts, uint8_t* __restrict__ restart) {
+#define VAD_HOP_SCORE 1
+#define VAD_HOP_DENOISE 1
+#define VAD_HOP_SESSIONS 1
+#include "stream_hop_ffn_body.inc"
+#undef VAD_HOP_SESSIONS
+#undef VAD_HOP_DENOISE
+#undef VAD_HOP_SCORE
+}
+
+template <class TH>
+static hipError_t launch_stream_hop_sessions_t(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net,
+                                               float* frames, int64_t fstride, int len, const void* hop,
+                                               int64_t hstride, int hlen, int64_t n_streams, int mfcc_n, float* ring,
+                                               int* count, uint8_t* labels, int n_hops, int64_t hop_kstride,
+                                               int64_t lab_kstride, int active, float* scores, int64_t score_kstride,
+                                               const HopDenoise* dn, const int* hop_counts, uint8_t* restart,
+                                               hipStream_t st) {
+  const size_t tables = (size_t)(blob_n + net.wraw_n) * sizeof(float);
+  if (dn)
+    return launch_hop_kernels<&stream_hop_sessions_denoise_kernel<7, TH>, &stream_hop_sessions_denoise_kernel<16, TH>>(
+        tables, len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, net, frames, fstride, len, (const TH*)hop, hstride,
+        hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, active, scores, score_kstride,
+        *dn, hop_counts, restart);
+  return launch_hop_kernels<&stream_hop_sessions_kernel<7, TH>, &stream_hop_sessions_kernel<16, TH>>(
+      tables, len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, net, frames, fstride, len, (const TH*)hop, hstride,
+      hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, active, scores, score_kstride,
+      hop_counts, restart);
 }
 
 template <class TH>
@@ -273,6 +336,19 @@ hipError_t launch_stream_hop_denoise(const float* blob, int blob_n, int nf, int 
   const auto launch = hop_bytes == 2 ? launch_stream_hop_denoise_t<int16_t> : launch_stream_hop_denoise_t<float>;
   return launch(blob, blob_n, nf, n_taps, net, frames, fstride, len, hop, hstride, hlen, n_streams, mfcc_n, ring,
                 count, labels, n_hops, hop_kstride, lab_kstride, active, scores, score_kstride, dn, st);
+}
+
+// the sessions form: scores may be null; dn null: no denoising
+hipError_t launch_stream_hop_sessions(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net,
+                                      float* frames, int64_t fstride, int len, const void* hop, int hop_bytes,
+                                      int64_t hstride, int hlen, int64_t n_streams, int mfcc_n, float* ring,
+                                      int* count, uint8_t* labels, int n_hops, int64_t hop_kstride,
+                                      int64_t lab_kstride, int active, float* scores, int64_t score_kstride,
+                                      const HopDenoise* dn, const int* hop_counts, uint8_t* restart, hipStream_t st) {
+  const auto launch = hop_bytes == 2 ? launch_stream_hop_sessions_t<int16_t> : launch_stream_hop_sessions_t<float>;
+  return launch(blob, blob_n, nf, n_taps, net, frames, fstride, len, hop, hstride, hlen, n_streams, mfcc_n, ring,
+                count, labels, n_hops, hop_kstride, lab_kstride, active, scores, score_kstride, dn, hop_counts,
+                restart, st);
 }
 
 // ---------------------------------------------------------------------------

@@ -44,7 +44,9 @@ __global__ __launch_bounds__(1024) void stream_hop_tree_kernel(
     int64_t hop_kstride, int64_t lab_kstride) {
 #define VAD_HOP_SCORE 0
 #define VAD_HOP_DENOISE 0
+#define VAD_HOP_SESSIONS 0
 #include "stream_hop_tree_body.inc"
+#undef VAD_HOP_SESSIONS
 #undef VAD_HOP_DENOISE
 #undef VAD_HOP_SCORE
 }
@@ -59,7 +61,9 @@ __global__ __launch_bounds__(1024) void stream_hop_tree_scores_kernel(
     int64_t score_kstride) {
 #define VAD_HOP_SCORE 1
 #define VAD_HOP_DENOISE 0
+#define VAD_HOP_SESSIONS 0
 #include "stream_hop_tree_body.inc"
+#undef VAD_HOP_SESSIONS
 #undef VAD_HOP_DENOISE
 #undef VAD_HOP_SCORE
 }
@@ -76,7 +80,46 @@ __global__ __launch_bounds__(1024) void stream_hop_tree_denoise_kernel(
     int64_t score_kstride, HopDenoise dn) {
 #define VAD_HOP_SCORE 1
 #define VAD_HOP_DENOISE 1
+#define VAD_HOP_SESSIONS 0
 #include "stream_hop_tree_body.inc"
+#undef VAD_HOP_SESSIONS
+#undef VAD_HOP_DENOISE
+#undef VAD_HOP_SCORE
+}
+
+// The sessions forms (stream_kernel.hip's stream_hop_sessions_kernel): the
+// scored kernel with nullable `scores`, without and with the denoise state,
+// plus the per-stream hop counts and restart flags.
+template <int NR, class TH>
+__global__ __launch_bounds__(1024) void stream_hop_tree_sessions_kernel(
+    const float* __restrict__ blob, int blob_n, int nf, int n_taps, const TreeNodeC* __restrict__ cnodes,
+    const TreeNode* __restrict__ nodes, int n_nodes, int lds_nodes, float* __restrict__ frames, int64_t fstride,
+    int len, const TH* __restrict__ hop, int64_t hstride, int hlen, int64_t n_streams, int mfcc_n,
+    float* __restrict__ ring, int* __restrict__ count, uint8_t* __restrict__ labels, int n_hops,
+    int64_t hop_kstride, int64_t lab_kstride, const float* __restrict__ node_score, float* __restrict__ scores,
+    int64_t score_kstride, const int* __restrict__ hop_counts, uint8_t* __restrict__ restart) {
+#define VAD_HOP_SCORE 1
+#define VAD_HOP_DENOISE 0
+#define VAD_HOP_SESSIONS 1
+#include "stream_hop_tree_body.inc"
+#undef VAD_HOP_SESSIONS
+#undef VAD_HOP_DENOISE
+#undef VAD_HOP_SCORE
+}
+
+template <int NR, class TH>
+__global__ __launch_bounds__(1024) void stream_hop_tree_sessions_denoise_kernel(
+    const float* __restrict__ blob, int blob_n, int nf, int n_taps, const TreeNodeC* __restrict__ cnodes,
+    const TreeNode* __restrict__ nodes, int n_nodes, int lds_nodes, float* __restrict__ frames, int64_t fstride,
+    int len, const TH* __restrict__ hop, int64_t hstride, int hlen, int64_t n_streams, int mfcc_n,
+    float* __restrict__ ring, int* __restrict__ count, uint8_t* __restrict__ labels, int n_hops,
+    int64_t hop_kstride, int64_t lab_kstride, const float* __restrict__ node_score, float* __restrict__ scores,
+    int64_t score_kstride, HopDenoise dn, const int* __restrict__ hop_counts, uint8_t* __restrict__ restart) {
+#define VAD_HOP_SCORE 1
+#define VAD_HOP_DENOISE 1
+#define VAD_HOP_SESSIONS 1
+#include "stream_hop_tree_body.inc"
+#undef VAD_HOP_SESSIONS
 #undef VAD_HOP_DENOISE
 #undef VAD_HOP_SCORE
 }
@@ -173,6 +216,45 @@ hipError_t launch_stream_hop_tree_denoise(const float* blob, int blob_n, int nf,
   return launch(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds ? n_nodes : 0, frames, fstride, len, hop,
                 hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, node_score,
                 scores, score_kstride, dn, st);
+}
+
+template <class TH>
+static hipError_t launch_stream_hop_tree_sessions_t(const float* blob, int blob_n, int nf, int n_taps,
+                                                    const TreeNodeC* cnodes, const TreeNode* nodes, int n_nodes,
+                                                    int lds_nodes, float* frames, int64_t fstride, int len,
+                                                    const void* hop, int64_t hstride, int hlen, int64_t n_streams,
+                                                    int mfcc_n, float* ring, int* count, uint8_t* labels, int n_hops,
+                                                    int64_t hop_kstride, int64_t lab_kstride, const float* node_score,
+                                                    float* scores, int64_t score_kstride, const HopDenoise* dn,
+                                                    const int* hop_counts, uint8_t* restart, hipStream_t st) {
+  const size_t tables = (size_t)blob_n * sizeof(float) + (size_t)lds_nodes * sizeof(TreeNodeC);
+  if (dn)
+    return launch_hop_kernels<&stream_hop_tree_sessions_denoise_kernel<7, TH>,
+                              &stream_hop_tree_sessions_denoise_kernel<16, TH>>(
+        tables, len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds_nodes, frames,
+        fstride, len, (const TH*)hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride,
+        lab_kstride, node_score, scores, score_kstride, *dn, hop_counts, restart);
+  return launch_hop_kernels<&stream_hop_tree_sessions_kernel<7, TH>, &stream_hop_tree_sessions_kernel<16, TH>>(
+      tables, len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds_nodes, frames, fstride,
+      len, (const TH*)hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride,
+      node_score, scores, score_kstride, hop_counts, restart);
+}
+
+// the sessions form (the same walk rule): scores and node_score may be null; dn null: no denoising
+hipError_t launch_stream_hop_tree_sessions(const float* blob, int blob_n, int nf, int n_taps, const TreeNodeC* cnodes,
+                                           const TreeNode* nodes, int n_nodes, bool force_global, float* frames,
+                                           int64_t fstride, int len, const void* hop, int hop_bytes, int64_t hstride,
+                                           int hlen, int64_t n_streams, int mfcc_n, float* ring, int* count,
+                                           uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
+                                           const float* node_score, float* scores, int64_t score_kstride,
+                                           const HopDenoise* dn, const int* hop_counts, uint8_t* restart,
+                                           hipStream_t st) {
+  const bool lds = !force_global && cnodes && n_nodes <= stream_tree_max_lds_nodes(blob_n);
+  const auto launch =
+      hop_bytes == 2 ? launch_stream_hop_tree_sessions_t<int16_t> : launch_stream_hop_tree_sessions_t<float>;
+  return launch(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds ? n_nodes : 0, frames, fstride, len, hop,
+                hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, node_score,
+                scores, score_kstride, dn, hop_counts, restart, st);
 }
 
 // ---------------------------------------------------------------------------

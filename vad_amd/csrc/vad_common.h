@@ -203,6 +203,23 @@ hipError_t launch_stream_hop_tree_denoise(const float* blob, int blob_n, int nf,
                                           uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
                                           const float* node_score, float* scores, int64_t score_kstride,
                                           const HopDenoise& dn, hipStream_t st);
+// The sessions hop kernels: the scored form (scores may be null), dn null for
+// no denoising, plus hop_counts (S) int32 -- the hops stream s takes from its
+// column of the block, clamped to 0..n_hops -- and restart (S) bytes, consumed
+hipError_t launch_stream_hop_sessions(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net,
+                                      float* frames, int64_t fstride, int len, const void* hop, int hop_bytes,
+                                      int64_t hstride, int hlen, int64_t n_streams, int mfcc_n, float* ring,
+                                      int* count, uint8_t* labels, int n_hops, int64_t hop_kstride,
+                                      int64_t lab_kstride, int active, float* scores, int64_t score_kstride,
+                                      const HopDenoise* dn, const int* hop_counts, uint8_t* restart, hipStream_t st);
+hipError_t launch_stream_hop_tree_sessions(const float* blob, int blob_n, int nf, int n_taps, const TreeNodeC* cnodes,
+                                           const TreeNode* nodes, int n_nodes, bool force_global, float* frames,
+                                           int64_t fstride, int len, const void* hop, int hop_bytes, int64_t hstride,
+                                           int hlen, int64_t n_streams, int mfcc_n, float* ring, int* count,
+                                           uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
+                                           const float* node_score, float* scores, int64_t score_kstride,
+                                           const HopDenoise* dn, const int* hop_counts, uint8_t* restart,
+                                           hipStream_t st);
 // n noise frames per stream, (S, n, len) fp32 / int16 (in_bytes 4 / 2), into
 // the noise rows, the count and the estimate
 hipError_t launch_stream_noise_load(const float* blob, const void* fr, int in_bytes, int64_t sstride, int64_t fstride,

@@ -75,6 +75,26 @@ units |X/512|^2 (the kernels keep |2X|^2: an exact factor 2^-20).  Not covered:
 the clip kernels (the loop is sequential in the frames), SKLearnAnalyzer,
 SimpleStreamBatch.
 
+Sessions: StreamBatch(..., sessions=True) lets streams join, leave and stall
+inside the hop kernel (vad_stream_hops_sessions and its _i16 / tree forms:
+still one kernel).  Two static device tensors are read at the start of every
+step: ``hop_counts`` (S,) int32, initially K -- stream s takes n_s =
+min(max(hop_counts[s], 0), K) hops from rows 0..n_s-1 of its column of the
+input block -- and ``restart`` (S,) uint8, initially 0 -- nonzero: the stream's
+state becomes what reset() makes it (with denoise=True its spectrum ring,
+noise rows, noise count and estimate too) before its hops, and the kernel
+stores 0 back, so a flag set once restarts once, also under graph replay.
+Label rows n_s..K-1 of a stream hold LABEL_NO_HOP (254), its score rows NaN; a
+stream with no hop and no restart keeps every byte of its state.  With all
+counts K and no restart everything equals a batch without sessions, bit for
+bit.  step / step_block take ``hop_counts=`` / ``restart=`` (copied into the
+static tensors); the host forms copy ``host_hop_counts`` / ``host_restart`` in
+before the kernel (the producer clears host_restart itself: the kernel
+consumes the device copy only).  Combines with FFN or tree, scores, denoise,
+int16 input, hops_per_step 1 or K, capture, step_host and HostPipeline (a
+pair per slot).  Not covered: kernel="three"; segmenter() (the online
+segmenter counts one window per label row); a StreamResampler in front.
+
 Blocks in flight: host_pipeline(depth) returns a HostPipeline with `depth`
 slots, each with pinned host buffers and a device input / label block of its
 own, and three streams (copy-in, compute, copy-out): submit(d) enqueues slot
@@ -97,6 +117,7 @@ from .plan import MfccPlan
 from .tree import TreeClassifier
 
 _TREE_WALKS = {"auto": _lib.TREE_WALK_AUTO, "global": _lib.TREE_WALK_GLOBAL}
+LABEL_NO_HOP = _lib.LABEL_NO_HOP  # VAD_LABEL_NO_HOP: a label row the stream has no hop in (sessions)
 
 
 def hop_rows_disjoint(n_streams, n_hops, block_stride, hop_stride, hop_len):
@@ -131,7 +152,10 @@ class StreamBatch:
 
     def __init__(self, n_streams, ffn, cfg: MfccConfig = MfccConfig(), device=None, kernel="hop",
                  hops_per_step=1, input_dtype=torch.float32, tree_walk="auto", scores=False, active=1,
-                 denoise=False, alpha=0.9, noise_class=0, noise_update=True):
+                 denoise=False, alpha=0.9, noise_class=0, noise_update=True, sessions=False):
+        self.sessions = bool(sessions)
+        if self.sessions and kernel == "three":
+            raise ValueError("sessions live in the one-kernel hop: kernel='three' has none")
         if input_dtype not in (torch.float32, torch.int16):
             raise ValueError("input_dtype must be torch.float32 or torch.int16")
         if tree_walk not in _TREE_WALKS:
@@ -198,10 +222,15 @@ class StreamBatch:
             self._noise = torch.zeros((S, 5, 256), dtype=torch.float32, device=dev)
             self._est = torch.zeros((S, 256), dtype=torch.float32, device=dev)
             self.noise_count = torch.zeros((S,), dtype=torch.int32, device=dev)
+        if self.sessions:  # read by the kernel at the start of every step; restart is consumed there
+            self.hop_counts = torch.full((S,), K, dtype=torch.int32, device=dev)
+            self.restart = torch.zeros((S,), dtype=torch.uint8, device=dev)
         self.graph = None
         self.graph_host_io = False
         self.host_inputs = None
         self.host_labels = None
+        self.host_hop_counts = None
+        self.host_restart = None
 
     _UNITS = 2.0 ** -20  # |2X|^2 -> |X/512|^2, exact
 
@@ -260,17 +289,39 @@ class StreamBatch:
         if self.denoise:
             for t in (self._spec, self._noise, self._est, self.noise_count):
                 t.zero_()
+        if self.sessions:
+            self.hop_counts.fill_(self.K)
+            self.restart.zero_()
 
-    def _hop_call(self, h, n_hops=1, labels=None, stream=None):
+    def _set_sessions(self, hop_counts, restart):
+        """Check the per-call tensors and copy them into the static ones."""
+        if hop_counts is None and restart is None:
+            return
+        if not self.sessions:
+            raise ValueError("hop_counts / restart: build the batch with sessions=True")
+        for t, dst, name in ((hop_counts, self.hop_counts, "hop_counts"), (restart, self.restart, "restart")):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.shape != dst.shape or t.dtype != dst.dtype:
+                raise ValueError(f"{name} must be a CUDA {str(dst.dtype).replace('torch.', '')} tensor of shape "
+                                 f"{tuple(dst.shape)}")
+        if hop_counts is not None:
+            self.hop_counts.copy_(hop_counts)
+        if restart is not None:
+            self.restart.copy_(restart)
+
+    def _hop_call(self, h, n_hops=1, labels=None, stream=None, sess=None):
         """vad_stream_hops (_i16 for an int16 batch) with the per-batch
         arguments prepared once (the Python side of a launch is a few
         microseconds of ctypes marshalling: per call only the hop block's
         address and strides change).  stream: a hipStream_t pointer, default
-        the current stream."""
+        the current stream.  sess: a sessions batch's (hop_counts, restart)
+        pointers, default the batch's own tensors."""
         if getattr(self, "_hop_head", None) is None:
             L = self.cfg.frame_size
             self._hop_name = ("vad_stream_hops_tree" if self.is_tree else "vad_stream_hops") + \
-                ("_denoise" if self.denoise else "_scores" if self.scores else "") + ("_i16" if self._i16 else "")
+                ("_sessions" if self.sessions else "_denoise" if self.denoise else "_scores" if self.scores else "") + \
+                ("_i16" if self._i16 else "")
             if self.scores and self.is_tree:
                 self.ffn.plan_with_scores()
             # rows [0, n_hops) of score_block, whichever label rows the call writes
@@ -279,6 +330,9 @@ class StreamBatch:
                 self._hop_scores = (self._hop_scores or (0, None, 0)) + (
                     _lib.ptr(self._spec), _lib.ptr(self._noise), _lib.ptr(self.noise_count), _lib.ptr(self._est),
                     self.alpha, self.noise_class, int(self.noise_update))
+            elif self.sessions:  # the denoising entry's arguments with a null state: no denoising
+                self._hop_scores = (self._hop_scores or (0, None, 0)) + (None, None, None, None, 0.0, 0, 0)
+            self._hop_sess = (_lib.ptr(self.hop_counts), _lib.ptr(self.restart)) if self.sessions else ()
             self._hop_fn = getattr(_lib.lib(), self._hop_name)
             self._hop_head = (self.plan.handle, self.ffn.plan.handle, _lib.ptr(self.frames), L, L)
             self._hop_mid = (_lib.ptr(self.ring), _lib.ptr(self.count))
@@ -292,7 +346,8 @@ class StreamBatch:
             self._hop_labels[key] = tail
         rc = self._hop_fn(*self._hop_head, ctypes.c_void_p(h.data_ptr()), h.stride(-2), self.cfg.hop, self.n,
                           n_hops, h.stride(0) if h.dim() == 3 else 0, *self._hop_mid, *tail, *self._hop_walk,
-                          *self._hop_scores, _lib.stream_ptr() if stream is None else stream)
+                          *self._hop_scores, *(self._hop_sess if sess is None else sess),
+                          _lib.stream_ptr() if stream is None else stream)
         if rc:
             _lib.check(rc, self._hop_name)
 
@@ -325,12 +380,15 @@ class StreamBatch:
             for k in range(self.K):
                 self._three(self.inputs[k], self.label_block[k])
 
-    def step(self, new_samples=None):
+    def step(self, new_samples=None, hop_counts=None, restart=None):
         """Advance every stream by one hop (new_samples: (S, hop) device
         tensor of the batch's input dtype; None: the hop already written into
-        ``hop_in``).  hops_per_step == 1."""
+        ``hop_in``).  hops_per_step == 1.  A sessions batch: hop_counts (S,)
+        int32 / restart (S,) uint8 device tensors are copied into the static
+        ``hop_counts`` / ``restart`` first; None leaves those as written."""
         if self.K != 1:
             raise ValueError("this batch advances hops_per_step hops at a time: use step_block")
+        self._set_sessions(hop_counts, restart)
         if new_samples is not None and (new_samples.shape != self.hop_in.shape
                                         or new_samples.dtype != self.input_dtype or not new_samples.is_cuda):
             raise ValueError(f"new_samples must be a CUDA {self._dtype_name} tensor of shape "
@@ -347,10 +405,13 @@ class StreamBatch:
             self._body()
         return self.labels
 
-    def step_block(self, new_samples=None):
+    def step_block(self, new_samples=None, hop_counts=None, restart=None):
         """Advance every stream by K = hops_per_step hops; new_samples: (K, S,
         hop) device tensor of the batch's input dtype, or None when the block was written into ``inputs``
-        (the graph's static input: no copy).  Returns label_block (K, S)."""
+        (the graph's static input: no copy).  Returns label_block (K, S).
+        hop_counts / restart: as step (a stream takes min(max(count, 0), K)
+        hops; the label rows past them hold LABEL_NO_HOP)."""
+        self._set_sessions(hop_counts, restart)
         if new_samples is not None:
             if new_samples.shape != self.inputs.shape or new_samples.dtype != self.input_dtype \
                     or not new_samples.is_cuda:
@@ -369,15 +430,22 @@ class StreamBatch:
 
     def attach_host_io(self):
         """Pinned host buffers for step_host: host_inputs (K, S, hop) of the
-        batch's input dtype, host_labels (K, S) uint8."""
+        batch's input dtype, host_labels (K, S) uint8; a sessions batch also
+        gets host_hop_counts (S,) int32 (K) and host_restart (S,) uint8 (0)."""
         if self.host_inputs is None:
             self.host_inputs = torch.zeros(tuple(self.inputs.shape), dtype=self.input_dtype, pin_memory=True)
             self.host_labels = torch.full(tuple(self.label_block.shape), 255, dtype=torch.uint8,
                                           pin_memory=True)
+            if self.sessions:
+                self.host_hop_counts = torch.full((self.n,), self.K, dtype=torch.int32, pin_memory=True)
+                self.host_restart = torch.zeros((self.n,), dtype=torch.uint8, pin_memory=True)
         return self.host_inputs, self.host_labels
 
     def _host_body(self):
         self.inputs.copy_(self.host_inputs, non_blocking=True)
+        if self.sessions:
+            self.hop_counts.copy_(self.host_hop_counts, non_blocking=True)
+            self.restart.copy_(self.host_restart, non_blocking=True)
         if self.K == 1:
             self._body()
         else:
@@ -413,6 +481,8 @@ class StreamBatch:
         saved = (self.frames.clone(), self.ring.clone(), self.count.clone(), self.label_block.clone())
         saved_scores = self.score_block.clone() if self.scores else None
         dn_state = (self._spec, self._noise, self._est, self.noise_count) if self.denoise else ()
+        if self.sessions:  # the warm-up consumes restart flags, and with host_io overwrites both tensors
+            dn_state += (self.hop_counts, self.restart)
         dn_saved = [t.clone() for t in dn_state]
         if host_io:
             self.attach_host_io()
@@ -465,6 +535,10 @@ class StreamBatch:
         (the batch must have scores=True) feed it ``score_block`` instead, and
         ``active`` is the batch's."""
         from .stream_segments import StreamSegmenter
+        if self.sessions:
+            raise ValueError("segmenter() on a sessions batch: the online segmenter counts one window per label "
+                             "row, so a row of LABEL_NO_HOP would shift its clock (per-stream flush and restart "
+                             "in the segmenter is not built)")
         if kw.get("on") is not None:
             if not self.scores:
                 raise ValueError("segmenter(on=...) reads score_block: build the batch with scores=True")
@@ -490,7 +564,10 @@ class HostPipeline:
 
     Slot d has pinned ``host_inputs[d]`` (K, S, hop; the batch's input dtype)
     and ``host_labels[d]`` (K, S; uint8), and a device input block and a device
-    label block of its own.  submit(d) enqueues
+    label block of its own; over a sessions batch also pinned
+    ``host_hop_counts[d]`` / ``host_restart[d]`` and a device pair of its own,
+    copied in with the input block (the batch's ``hop_counts`` / ``restart``
+    are not read).  submit(d) enqueues
       the H2D copy of host_inputs[d] on the copy-in stream, after slot d's
         previous kernel has finished with the device input block;
       the hop kernel(s) on the compute stream, after that copy and after slot
@@ -517,6 +594,13 @@ class HostPipeline:
         self.host_labels = [torch.full(lshape, 255, dtype=torch.uint8, pin_memory=True) for _ in range(depth)]
         self._dev_in = [torch.zeros(ishape, dtype=batch.input_dtype, device=dev) for _ in range(depth)]
         self._dev_lab = [torch.full(lshape, 255, dtype=torch.uint8, device=dev) for _ in range(depth)]
+        if batch.sessions:  # a pair per slot: slot d + 1's copy-in may run while slot d's kernel reads its own
+            S, K = batch.n, batch.K
+            self.host_hop_counts = [torch.full((S,), K, dtype=torch.int32, pin_memory=True) for _ in range(depth)]
+            self.host_restart = [torch.zeros((S,), dtype=torch.uint8, pin_memory=True) for _ in range(depth)]
+            self._dev_cnt = [torch.full((S,), K, dtype=torch.int32, device=dev) for _ in range(depth)]
+            self._dev_rst = [torch.zeros((S,), dtype=torch.uint8, device=dev) for _ in range(depth)]
+            self._sess = [(_lib.ptr(c), _lib.ptr(r)) for c, r in zip(self._dev_cnt, self._dev_rst)]
         self.copy_in, self.compute, self.copy_out = (torch.cuda.Stream(device=dev) for _ in range(3))
         self._run_ptr = ctypes.c_void_p(self.compute.cuda_stream)
         self._h2d = [torch.cuda.Event() for _ in range(depth)]
@@ -546,12 +630,16 @@ class HostPipeline:
                 self.copy_in.wait_event(self._ran[d])
             torch.cuda.set_stream(self.copy_in)
             self._dev_in[d].copy_(self.host_inputs[d], non_blocking=True)
+            if b.sessions:
+                self._dev_cnt[d].copy_(self.host_hop_counts[d], non_blocking=True)
+                self._dev_rst[d].copy_(self.host_restart[d], non_blocking=True)
             self._h2d[d].record(self.copy_in)
             self.compute.wait_event(self._h2d[d])
             if used:
                 self.compute.wait_event(self._d2h[d])
             if b.kernel == "hop":
-                b._hop_call(self._dev_in[d], b.K, self._dev_lab[d], self._run_ptr)
+                b._hop_call(self._dev_in[d], b.K, self._dev_lab[d], self._run_ptr,
+                            self._sess[d] if b.sessions else None)
             else:
                 for k in range(b.K):
                     b._three(self._dev_in[d][k], self._dev_lab[d][k], self._run_ptr)
