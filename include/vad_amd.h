@@ -1219,6 +1219,106 @@ int vad_stream_segments_op_flush_i16(int64_t n_streams, int32_t block_is_scores,
                                      int64_t* found, int16_t* history, int64_t history_elems, int16_t* voiced,
                                      int32_t* voiced_len, void* stream);
 
+/* Sessions in the streaming segmenter: the push entries above for the label
+ * (or score) and hop blocks of vad_stream_hops_sessions*, where streams join,
+ * leave and stall inside one launch.  Still one kernel, one wave per stream,
+ * no atomics, no barrier, no wave waits on another.  The flush entries above
+ * serve a sessions state unchanged (they end every stream).
+ *   hop counts  hop_counts (S) int32 and restart (S) uint8 are read once per
+ *               stream at the start of the launch.  Stream s takes n_s =
+ *               min(max(hop_counts[s], 0), n_hops) hops: rows 0..n_s-1 of its
+ *               column of the block and of the hop samples, the rows the
+ *               sessions hop kernel consumed.  Its clock, history and
+ *               decisions advance by n_s.  Rows n_s..n_hops-1 are never read,
+ *               whatever they hold; voiced_len[n_s..n_hops-1, s] = 0 and
+ *               nothing of `voiced` is written there.  A stream with n_s = 0
+ *               and no restart keeps every byte of its state, history slice,
+ *               found and table rows; only its voiced_len and end_len rows
+ *               are written, as zeros.
+ *   restart     restart[s] != 0: the kernel stores 0 back (a flag set once
+ *               restarts once, also under graph replay; the flag is the
+ *               segmenter's own, the hop kernel has cleared its own by then)
+ *               and, before the stream's hops,
+ *               1. ends the running session: what the flush entry does, for
+ *                  this stream alone -- F = vad_stream_seg_flush_rows(_pad)
+ *                  hops of inactive windows without samples, the newest padded
+ *                  end stopped at window N - 1, finished rows appended, the
+ *                  voiced prefixes to end_voiced (F x S x hop) / end_len
+ *                  (F x S).  end_len[:, s] is written for every stream by
+ *                  every call, zeros where no session ended (so also for a
+ *                  fresh stream, t = 0, and for one a flush entry ended: no
+ *                  rows are appended for those).  The events-only entries
+ *                  write end_len too: the lengths the prefixes would have;
+ *               2. makes the stream fresh: the state as zeroed -- hysteresis
+ *                  bit and `ended` included -- but for a session ordinal that
+ *                  goes up by one per consumed flag (all zero is still a
+ *                  fresh state, ordinal 0; the state's size does not change),
+ *                  and the L - H carry positions of its history slice zeroed;
+ *               3. then the stream takes its n_s hops.  Sample positions in
+ *                  rows, and the equivalent clip, start again at 0.
+ *   table       segments and found keep appending across sessions (found
+ *               counts past capacity as before); table_session (S x capacity)
+ *               int32 gets the session ordinal of every row written.  The
+ *               flush entries know no sessions and do not write it: the rows
+ *               they append, [found before, found after) of a stream, belong
+ *               to its running session (vad_amd.stream_segments files them).
+ *   equality    per stream and session, the rows and the concatenation of the
+ *               session's voiced prefixes, push rows then end rows, equal a
+ *               one-stream vad_stream_segments* pushed with that session's
+ *               hops and flushed, bit for bit; with every count n_hops and no
+ *               flag, state, history, segments, found, voiced and voiced_len
+ *               equal the sibling entry's byte for byte.
+ *   history     the sibling's bound R >= (D+3)H + L + n_hops*H still holds:
+ *               ending a session appends no samples and comes before the
+ *               block's hops are written.
+ * Refusals: the sibling's, plus VAD_EINVAL for a NULL hop_counts, restart,
+ * end_len, table_session (with capacity > 0) or, in the audio forms,
+ * end_voiced, and for one of them misaligned for its type. */
+int vad_stream_segments_sessions(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams,
+                                 int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run,
+                                 int32_t frame_size, int32_t hop, void* state, int64_t* segments, int64_t capacity,
+                                 int64_t* found, const int32_t* hop_counts, uint8_t* restart, int32_t* end_len,
+                                 int32_t* table_session, void* stream);
+int vad_stream_segments_sessions_f32(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams,
+                                     int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run,
+                                     int32_t frame_size, int32_t hop, void* state, int64_t* segments,
+                                     int64_t capacity, int64_t* found, const float* hop_samples, int64_t hop_stride,
+                                     int64_t hop_block_stride, float* history, int64_t history_elems, float* voiced,
+                                     int32_t* voiced_len, const int32_t* hop_counts, uint8_t* restart,
+                                     float* end_voiced, int32_t* end_len, int32_t* table_session, void* stream);
+int vad_stream_segments_sessions_i16(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams,
+                                     int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run,
+                                     int32_t frame_size, int32_t hop, void* state, int64_t* segments,
+                                     int64_t capacity, int64_t* found, const int16_t* hop_samples,
+                                     int64_t hop_stride, int64_t hop_block_stride, int16_t* history,
+                                     int64_t history_elems, int16_t* voiced, int32_t* voiced_len,
+                                     const int32_t* hop_counts, uint8_t* restart, int16_t* end_voiced,
+                                     int32_t* end_len, int32_t* table_session, void* stream);
+int vad_stream_segments_op_sessions(const void* block, int32_t block_is_scores, int64_t block_stride,
+                                    int64_t n_streams, int32_t n_hops, int32_t active, int64_t max_gap,
+                                    int64_t min_run, int32_t frame_size, int32_t hop, float on, float off,
+                                    int64_t pad_before, int64_t pad_after, void* state, int64_t* segments,
+                                    int64_t capacity, int64_t* found, const int32_t* hop_counts, uint8_t* restart,
+                                    int32_t* end_len, int32_t* table_session, void* stream);
+int vad_stream_segments_op_sessions_f32(const void* block, int32_t block_is_scores, int64_t block_stride,
+                                        int64_t n_streams, int32_t n_hops, int32_t active, int64_t max_gap,
+                                        int64_t min_run, int32_t frame_size, int32_t hop, float on, float off,
+                                        int64_t pad_before, int64_t pad_after, void* state, int64_t* segments,
+                                        int64_t capacity, int64_t* found, const float* hop_samples,
+                                        int64_t hop_stride, int64_t hop_block_stride, float* history,
+                                        int64_t history_elems, float* voiced, int32_t* voiced_len,
+                                        const int32_t* hop_counts, uint8_t* restart, float* end_voiced,
+                                        int32_t* end_len, int32_t* table_session, void* stream);
+int vad_stream_segments_op_sessions_i16(const void* block, int32_t block_is_scores, int64_t block_stride,
+                                        int64_t n_streams, int32_t n_hops, int32_t active, int64_t max_gap,
+                                        int64_t min_run, int32_t frame_size, int32_t hop, float on, float off,
+                                        int64_t pad_before, int64_t pad_after, void* state, int64_t* segments,
+                                        int64_t capacity, int64_t* found, const int16_t* hop_samples,
+                                        int64_t hop_stride, int64_t hop_block_stride, int16_t* history,
+                                        int64_t history_elems, int16_t* voiced, int32_t* voiced_len,
+                                        const int32_t* hop_counts, uint8_t* restart, int16_t* end_voiced,
+                                        int32_t* end_len, int32_t* table_session, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Resampling: audio at another rate to the front end's (the mel bank, the
  * 400 / 160 framing and the classifiers assume 16 kHz; the reference has no

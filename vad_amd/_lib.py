@@ -215,6 +215,21 @@ SIGNATURES = {
     **{"vad_stream_segments_op_flush_" + t: (c_int, [c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_f32, c_f32, c_i64,
                                                      c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp])
        for t in ("f32", "i16")},
+    # sessions: the sibling's arguments, then hop_counts, restart, (end_voiced,) end_len, table_session, stream
+    "vad_stream_segments_sessions": (c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32, c_vp,
+                                             c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    **{"vad_stream_segments_sessions_" + t: (c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32,
+                                                     c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp,
+                                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp])
+       for t in ("f32", "i16")},
+    "vad_stream_segments_op_sessions": (c_int, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32,
+                                                c_f32, c_f32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                                c_vp, c_vp, c_vp]),
+    **{"vad_stream_segments_op_sessions_" + t: (c_int, [c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_i32,
+                                                        c_i32, c_f32, c_f32, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp,
+                                                        c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                                        c_vp, c_vp, c_vp, c_vp])
+       for t in ("f32", "i16")},
     "vad_resample_tile_outputs": (c_i32, []),
     "vad_resample_plan_create": (c_int, [c_i32, c_i32, c_vp, c_i32, c_vp]),
     "vad_resample_plan_upload": (c_int, [c_vp]),

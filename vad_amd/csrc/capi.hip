@@ -1689,6 +1689,16 @@ struct SegOpHost {
   int64_t pad_before, pad_after;
 };
 
+// The sessions entries' five pointers (vad_stream_segments_sessions*); null
+// for every other entry.
+struct SegSessHost {
+  const int32_t* hop_counts;
+  uint8_t* restart;
+  void* end_voiced;
+  int32_t* end_len;
+  int32_t* table_session;
+};
+
 // One body for the six entries: labels == NULL with flush set is a flush of
 // vad_stream_seg_flush_rows hops; audio_bytes 0 is the events-only form.
 // Every check comes before any HIP call, in the same order for every form.
@@ -1697,7 +1707,8 @@ static int stream_segments_entry(bool flush, const uint8_t* labels, int64_t labe
                                  int32_t frame_size, int32_t hop, void* state, int64_t* segments, int64_t capacity,
                                  int64_t* found, int audio_bytes, const void* hop_samples, int64_t hop_stride,
                                  int64_t hop_block_stride, void* history, int64_t history_elems, void* voiced,
-                                 int32_t* voiced_len, void* stream, const SegOpHost* op = nullptr) {
+                                 int32_t* voiced_len, void* stream, const SegOpHost* op = nullptr,
+                                 const SegSessHost* sess = nullptr) {
   const int64_t delay = op ? vad_stream_seg_delay_pad(max_gap, min_run, frame_size, hop, op->pad_before, op->pad_after)
                            : vad_stream_seg_delay(max_gap, min_run, frame_size, hop);
   if (delay < 0) return VAD_EINVAL;  // hop outside (0, frame_size], a negative gap, run or pad
@@ -1721,6 +1732,15 @@ static int stream_segments_entry(bool flush, const uint8_t* labels, int64_t labe
   if (reinterpret_cast<uintptr_t>(state) % 8 || reinterpret_cast<uintptr_t>(segments) % 8 ||
       reinterpret_cast<uintptr_t>(found) % 8)
     return VAD_EINVAL;
+  if (sess) {
+    if (!sess->hop_counts || !sess->restart || !sess->end_len || (capacity > 0 && !sess->table_session))
+      return VAD_EINVAL;
+    if (audio_bytes && !sess->end_voiced) return VAD_EINVAL;
+    if (reinterpret_cast<uintptr_t>(sess->hop_counts) % 4 || reinterpret_cast<uintptr_t>(sess->end_len) % 4 ||
+        reinterpret_cast<uintptr_t>(sess->table_session) % 4 ||
+        (audio_bytes && reinterpret_cast<uintptr_t>(sess->end_voiced) % audio_bytes))
+      return VAD_EINVAL;
+  }
   SegStreamArgs a{};
   if (audio_bytes) {
     if ((!flush && !hop_samples) || !history || !voiced || !voiced_len) return VAD_EINVAL;
@@ -1739,13 +1759,21 @@ static int stream_segments_entry(bool flush, const uint8_t* labels, int64_t labe
   a.max_gap = max_gap, a.min_run = min_run, a.join = frame_size / hop - 1, a.delay = delay;
   a.frame_size = frame_size, a.hop = hop;
   a.state = state, a.segments = segments, a.capacity = capacity, a.found = found;
+  SegSessArgs ss{};
+  if (sess) {  // the end of a session is that stream's flush: as many rows
+    ss.hop_counts = sess->hop_counts, ss.restart = sess->restart, ss.end_voiced = sess->end_voiced;
+    ss.end_len = sess->end_len, ss.table_session = sess->table_session;
+    ss.flush_rows = (int)(delay + 2 + (frame_size + hop - 1) / hop);
+  }
   if (op) {
     if (!flush && op->block_is_scores && reinterpret_cast<uintptr_t>(labels) % 4) return VAD_EINVAL;
     SegOpArgs o{};
     o.on = op->on, o.off = op->off, o.is_scores = op->block_is_scores;
     o.pad_before = op->pad_before, o.pad_after = op->pad_after;
+    if (sess) return (int)launch_stream_segments_sessions(a, &o, ss, audio_bytes, (hipStream_t)stream);
     return (int)launch_stream_segments_op(a, o, audio_bytes, (hipStream_t)stream);
   }
+  if (sess) return (int)launch_stream_segments_sessions(a, nullptr, ss, audio_bytes, (hipStream_t)stream);
   return (int)launch_stream_segments(a, audio_bytes, (hipStream_t)stream);
 }
 
@@ -1878,6 +1906,94 @@ int vad_stream_segments_op_flush_i16(int64_t n_streams, int32_t block_is_scores,
                                1, max_gap, min_run, frame_size, hop, state, segments, capacity, found, 2, nullptr, 0,
                                0, history, history_elems, voiced, voiced_len, stream, &oph);
 }
+
+// The sessions forms of a push (include/vad_amd.h, "Sessions in the streaming
+// segmenter"): the siblings' arguments and checks, plus the five pointers.
+#define VAD_SEG_SESS_HOST(ev) const SegSessHost ssh{hop_counts, restart, ev, end_len, table_session}
+
+int vad_stream_segments_sessions(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams,
+                                 int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run,
+                                 int32_t frame_size, int32_t hop, void* state, int64_t* segments, int64_t capacity,
+                                 int64_t* found, const int32_t* hop_counts, uint8_t* restart, int32_t* end_len,
+                                 int32_t* table_session, void* stream) {
+  VAD_SEG_SESS_HOST(nullptr);
+  return stream_segments_entry(false, labels, label_block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 0, nullptr, 0, 0, nullptr, 0,
+                               nullptr, nullptr, stream, nullptr, &ssh);
+}
+
+int vad_stream_segments_sessions_f32(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams,
+                                     int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run,
+                                     int32_t frame_size, int32_t hop, void* state, int64_t* segments,
+                                     int64_t capacity, int64_t* found, const float* hop_samples, int64_t hop_stride,
+                                     int64_t hop_block_stride, float* history, int64_t history_elems, float* voiced,
+                                     int32_t* voiced_len, const int32_t* hop_counts, uint8_t* restart,
+                                     float* end_voiced, int32_t* end_len, int32_t* table_session, void* stream) {
+  VAD_SEG_SESS_HOST(end_voiced);
+  return stream_segments_entry(false, labels, label_block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 4, hop_samples, hop_stride,
+                               hop_block_stride, history, history_elems, voiced, voiced_len, stream, nullptr, &ssh);
+}
+
+int vad_stream_segments_sessions_i16(const uint8_t* labels, int64_t label_block_stride, int64_t n_streams,
+                                     int32_t n_hops, int32_t active, int64_t max_gap, int64_t min_run,
+                                     int32_t frame_size, int32_t hop, void* state, int64_t* segments,
+                                     int64_t capacity, int64_t* found, const int16_t* hop_samples,
+                                     int64_t hop_stride, int64_t hop_block_stride, int16_t* history,
+                                     int64_t history_elems, int16_t* voiced, int32_t* voiced_len,
+                                     const int32_t* hop_counts, uint8_t* restart, int16_t* end_voiced,
+                                     int32_t* end_len, int32_t* table_session, void* stream) {
+  VAD_SEG_SESS_HOST(end_voiced);
+  return stream_segments_entry(false, labels, label_block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 2, hop_samples, hop_stride,
+                               hop_block_stride, history, history_elems, voiced, voiced_len, stream, nullptr, &ssh);
+}
+
+int vad_stream_segments_op_sessions(const void* block, int32_t block_is_scores, int64_t block_stride,
+                                    int64_t n_streams, int32_t n_hops, int32_t active, int64_t max_gap,
+                                    int64_t min_run, int32_t frame_size, int32_t hop, float on, float off,
+                                    int64_t pad_before, int64_t pad_after, void* state, int64_t* segments,
+                                    int64_t capacity, int64_t* found, const int32_t* hop_counts, uint8_t* restart,
+                                    int32_t* end_len, int32_t* table_session, void* stream) {
+  VAD_SEG_OP_HOST;
+  VAD_SEG_SESS_HOST(nullptr);
+  return stream_segments_entry(false, (const uint8_t*)block, block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 0, nullptr, 0, 0, nullptr, 0,
+                               nullptr, nullptr, stream, &oph, &ssh);
+}
+
+int vad_stream_segments_op_sessions_f32(const void* block, int32_t block_is_scores, int64_t block_stride,
+                                        int64_t n_streams, int32_t n_hops, int32_t active, int64_t max_gap,
+                                        int64_t min_run, int32_t frame_size, int32_t hop, float on, float off,
+                                        int64_t pad_before, int64_t pad_after, void* state, int64_t* segments,
+                                        int64_t capacity, int64_t* found, const float* hop_samples,
+                                        int64_t hop_stride, int64_t hop_block_stride, float* history,
+                                        int64_t history_elems, float* voiced, int32_t* voiced_len,
+                                        const int32_t* hop_counts, uint8_t* restart, float* end_voiced,
+                                        int32_t* end_len, int32_t* table_session, void* stream) {
+  VAD_SEG_OP_HOST;
+  VAD_SEG_SESS_HOST(end_voiced);
+  return stream_segments_entry(false, (const uint8_t*)block, block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 4, hop_samples, hop_stride,
+                               hop_block_stride, history, history_elems, voiced, voiced_len, stream, &oph, &ssh);
+}
+
+int vad_stream_segments_op_sessions_i16(const void* block, int32_t block_is_scores, int64_t block_stride,
+                                        int64_t n_streams, int32_t n_hops, int32_t active, int64_t max_gap,
+                                        int64_t min_run, int32_t frame_size, int32_t hop, float on, float off,
+                                        int64_t pad_before, int64_t pad_after, void* state, int64_t* segments,
+                                        int64_t capacity, int64_t* found, const int16_t* hop_samples,
+                                        int64_t hop_stride, int64_t hop_block_stride, int16_t* history,
+                                        int64_t history_elems, int16_t* voiced, int32_t* voiced_len,
+                                        const int32_t* hop_counts, uint8_t* restart, int16_t* end_voiced,
+                                        int32_t* end_len, int32_t* table_session, void* stream) {
+  VAD_SEG_OP_HOST;
+  VAD_SEG_SESS_HOST(end_voiced);
+  return stream_segments_entry(false, (const uint8_t*)block, block_stride, n_streams, n_hops, active, max_gap, min_run,
+                               frame_size, hop, state, segments, capacity, found, 2, hop_samples, hop_stride,
+                               hop_block_stride, history, history_elems, voiced, voiced_len, stream, &oph, &ssh);
+}
+#undef VAD_SEG_SESS_HOST
 #undef VAD_SEG_OP_HOST
 
 // Replay of a captured graph (a hop block with its host copies,

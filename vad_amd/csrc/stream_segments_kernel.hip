@@ -66,6 +66,25 @@
 // still needed is overwritten while R >= (D+3)H + L + n_hops * H.  A prefix
 // can lie in hops of the same launch; the wave's stores are drained and
 // fenced (workgroup scope: one L1 per CU) before its first read.
+//
+// Sessions (stream_segments_sessions_kernel, stream_segments_op_sessions_kernel;
+// include/vad_amd.h, "Sessions in the streaming segmenter").  The wave reads
+// its stream's hop count and restart flag once, makes both scalar, and takes
+// n_s = min(max(count, 0), n_hops) hops: a loop bound.  A set flag is cleared
+// by lane 0 and, before the hops, (1) ends the running session -- the F flush
+// hops of this stream alone, as the first iterations of the one loop that
+// also runs the live hops (one expansion of stream_segments_step.inc), rows
+// appended, prefixes to end_voiced / end_len -- and (2) makes the state fresh but for the session ordinal in pad[0],
+// zeroing the L - H carry positions at the slice's top.  The prefix reads of
+// (1) are drained before the stores of (2), and those and the block's hops
+// are drained and fenced before the new session's first prefix read, by the
+// fence above.  The ring bound is unchanged: the end flush appends no samples
+// and runs before the block's hops are written, so it reads what a flush
+// entry would read (R >= (D+3)H + L, the bound at n_hops = 0); the new session
+// then starts at index 0 and writes n_s * H <= n_hops * H elements, and its
+// prefixes start at clip position 2H: in the zeroed carry or in those hops,
+// never in what the old session left.  A stream with no hop and no restart
+// returns before any store to its state, history, found or table.
 #include "vad_common.h"
 
 namespace vad {
@@ -80,7 +99,7 @@ struct SegStreamState {
   int32_t wpos;      // history index of the next hop's first sample
   int32_t ended;     // flushed: every further row is empty until the state is zeroed
   int32_t hyst;      // the operating-point forms' hysteresis decision h (one bit; 0 before the first window)
-  int32_t pad[2];
+  int32_t pad[2];    // pad[0]: the session ordinal (sessions kernels: restarts consumed so far)
 };
 static_assert(sizeof(SegStreamState) == kSegStreamStateBytes, "the sizing entry's bytes per stream");
 
@@ -92,14 +111,40 @@ constexpr int kSegStreamWaves = 4;
 template <class T, bool AUDIO>
 __global__ __launch_bounds__(64 * kSegStreamWaves) void stream_segments_kernel(SegStreamArgs a) {
 #define VAD_SEG_OP 0
+#define VAD_SEG_SESSIONS 0
 #include "stream_segments_body.inc"
+#undef VAD_SEG_SESSIONS
 #undef VAD_SEG_OP
 }
 
 template <class T, bool AUDIO, bool SCORES>
 __global__ __launch_bounds__(64 * kSegStreamWaves) void stream_segments_op_kernel(SegStreamArgs a, SegOpArgs op) {
 #define VAD_SEG_OP 1
+#define VAD_SEG_SESSIONS 0
 #include "stream_segments_body.inc"
+#undef VAD_SEG_SESSIONS
+#undef VAD_SEG_OP
+}
+
+// The sessions forms: the same bodies with per-stream hop counts and restarts.
+template <class T, bool AUDIO>
+__global__ __launch_bounds__(64 * kSegStreamWaves) void stream_segments_sessions_kernel(SegStreamArgs a,
+                                                                                        SegSessArgs ss) {
+#define VAD_SEG_OP 0
+#define VAD_SEG_SESSIONS 1
+#include "stream_segments_body.inc"
+#undef VAD_SEG_SESSIONS
+#undef VAD_SEG_OP
+}
+
+template <class T, bool AUDIO, bool SCORES>
+__global__ __launch_bounds__(64 * kSegStreamWaves) void stream_segments_op_sessions_kernel(SegStreamArgs a,
+                                                                                           SegOpArgs op,
+                                                                                           SegSessArgs ss) {
+#define VAD_SEG_OP 1
+#define VAD_SEG_SESSIONS 1
+#include "stream_segments_body.inc"
+#undef VAD_SEG_SESSIONS
 #undef VAD_SEG_OP
 }
 
@@ -120,6 +165,18 @@ hipError_t launch_op_t(const SegStreamArgs& a, const SegOpArgs& op, hipStream_t 
   return hipGetLastError();
 }
 
+template <class T, bool AUDIO>
+hipError_t launch_sessions_t(const SegStreamArgs& a, const SegOpArgs* op, const SegSessArgs& ss, hipStream_t st) {
+  const dim3 grid((unsigned)((a.n_streams + kSegStreamWaves - 1) / kSegStreamWaves)), block(64 * kSegStreamWaves);
+  if (!op)
+    hipLaunchKernelGGL((stream_segments_sessions_kernel<T, AUDIO>), grid, block, 0, st, a, ss);
+  else if (op->is_scores)
+    hipLaunchKernelGGL((stream_segments_op_sessions_kernel<T, AUDIO, true>), grid, block, 0, st, a, *op, ss);
+  else
+    hipLaunchKernelGGL((stream_segments_op_sessions_kernel<T, AUDIO, false>), grid, block, 0, st, a, *op, ss);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_stream_segments(const SegStreamArgs& a, int audio_bytes, hipStream_t st) {
@@ -136,6 +193,15 @@ hipError_t launch_stream_segments_op(const SegStreamArgs& a, const SegOpArgs& op
   if (audio_bytes == 4) return launch_op_t<float, true>(a, op, st);
   if (audio_bytes == 2) return launch_op_t<int16_t, true>(a, op, st);
   return launch_op_t<int16_t, false>(a, op, st);
+}
+
+// The sessions forms of a push (op == nullptr: the label kernel).
+hipError_t launch_stream_segments_sessions(const SegStreamArgs& a, const SegOpArgs* op, const SegSessArgs& ss,
+                                           int audio_bytes, hipStream_t st) {
+  if (a.n_streams <= 0 || a.n_hops <= 0) return hipSuccess;
+  if (audio_bytes == 4) return launch_sessions_t<float, true>(a, op, ss, st);
+  if (audio_bytes == 2) return launch_sessions_t<int16_t, true>(a, op, ss, st);
+  return launch_sessions_t<int16_t, false>(a, op, ss, st);
 }
 
 }  // namespace vad

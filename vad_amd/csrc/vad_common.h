@@ -261,6 +261,20 @@ struct SegOpArgs {
   int64_t pad_before, pad_after;  // windows
 };
 hipError_t launch_stream_segments_op(const SegStreamArgs& a, const SegOpArgs& op, int audio_bytes, hipStream_t st);
+// The sessions forms of a push (never a flush: a.labels is the block): stream
+// s takes min(max(hop_counts[s], 0), n_hops) hops; restart[s] != 0 ends its
+// session first (flush_rows hops into end_voiced / end_len) and is cleared.
+// A kernel argument of its own, so the kernels above keep theirs.
+struct SegSessArgs {
+  const int32_t* hop_counts;  // S
+  uint8_t* restart;           // S
+  void* end_voiced;           // flush_rows x S x hop (audio forms)
+  int32_t* end_len;           // flush_rows x S
+  int32_t* table_session;     // S x capacity: the session ordinal of each row of a.segments
+  int flush_rows;
+};
+hipError_t launch_stream_segments_sessions(const SegStreamArgs& a, const SegOpArgs* op, const SegSessArgs& ss,
+                                           int audio_bytes, hipStream_t st);
 // any fft_n other than 512 (spec_generic.hip): mode 0 frames -> MFCC,
 // 1 frames -> spectra, 2 spectra -> MFCC; tw = exp(-2 pi i m / fft_n), fp64
 hipError_t launch_generic(int mode, const MfccDev* plan, const float* src, int64_t stride, int len, int64_t n,

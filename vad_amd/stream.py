@@ -92,8 +92,18 @@ static tensors); the host forms copy ``host_hop_counts`` / ``host_restart`` in
 before the kernel (the producer clears host_restart itself: the kernel
 consumes the device copy only).  Combines with FFN or tree, scores, denoise,
 int16 input, hops_per_step 1 or K, capture, step_host and HostPipeline (a
-pair per slot).  Not covered: kernel="three"; segmenter() (the online
-segmenter counts one window per label row); a StreamResampler in front.
+pair per slot).  segmenter(sessions=True) returns the online segmenter's
+sessions form (vad_amd.stream_segments): it reads this batch's ``hop_counts``
+(both kernels read it, neither writes it) and owns a ``restart`` of its own,
+because the hop kernel has cleared the batch's by the time the segmenter
+runs; step / step_block copy a ``restart=`` they are given into it as well, so
+``sb.step_block(x, hop_counts=c, restart=r); seg.push(sb.label_block,
+sb.inputs)`` is the whole loop.  A caller that writes ``sb.restart`` directly
+(for a replayed graph) writes ``seg.restart`` too.  Not covered:
+kernel="three"; segmenter() without sessions=True (the plain online segmenter
+counts one window per label row); feeding the segmenter from step_host /
+HostPipeline (the caller copies ``host_restart`` into ``seg.restart`` itself);
+a StreamResampler in front.
 
 Blocks in flight: host_pipeline(depth) returns a HostPipeline with `depth`
 slots, each with pinned host buffers and a device input / label block of its
@@ -229,6 +239,7 @@ class StreamBatch:
         self.graph_host_io = False
         self.host_inputs = None
         self.host_labels = None
+        self._session_segmenters = weakref.WeakSet()  # segmenter(sessions=True): handed restart= by _set_sessions
         self.host_hop_counts = None
         self.host_restart = None
 
@@ -309,6 +320,8 @@ class StreamBatch:
             self.hop_counts.copy_(hop_counts)
         if restart is not None:
             self.restart.copy_(restart)
+            for seg in self._session_segmenters:  # each consumes a flag of its own
+                seg.restart.copy_(restart)
 
     def _hop_call(self, h, n_hops=1, labels=None, stream=None, sess=None):
         """vad_stream_hops (_i16 for an int16 batch) with the per-batch
@@ -527,24 +540,34 @@ class StreamBatch:
         between two synchronisations, not both at once."""
         return HostPipeline(self, depth)
 
-    def segmenter(self, **kw):
+    def segmenter(self, sessions=False, **kw):
         """A StreamSegmenter (vad_amd.stream_segments) matching this batch's
         streams, framing, hops per step and input dtype; kw: max_gap, min_run,
         active, capacity, on, off, pad.  Feed it ``label_block`` and ``inputs``
         (or the blocks step_block read in place) after each step; with ``on``
         (the batch must have scores=True) feed it ``score_block`` instead, and
-        ``active`` is the batch's."""
+        ``active`` is the batch's.  A sessions batch takes sessions=True: the
+        segmenter's ``hop_counts`` is this batch's tensor, and the ``restart=``
+        given to step / step_block is copied into its ``restart`` too (the
+        batch holds it weakly)."""
         from .stream_segments import StreamSegmenter
-        if self.sessions:
+        if self.sessions and not sessions:
             raise ValueError("segmenter() on a sessions batch: the online segmenter counts one window per label "
-                             "row, so a row of LABEL_NO_HOP would shift its clock (per-stream flush and restart "
-                             "in the segmenter is not built)")
+                             "row, so a row of LABEL_NO_HOP would shift its clock; segmenter(sessions=True) "
+                             "follows the per-stream hop counts and restarts")
+        if sessions and not self.sessions:
+            raise ValueError("segmenter(sessions=True): build the batch with sessions=True")
+        if sessions:
+            kw.update(sessions=True, hop_counts=self.hop_counts)
         if kw.get("on") is not None:
             if not self.scores:
                 raise ValueError("segmenter(on=...) reads score_block: build the batch with scores=True")
             kw.setdefault("active", self.active)
-        return StreamSegmenter(self.n, self.cfg, hops_per_step=self.K, audio_dtype=self.input_dtype,
-                               device=self.frames.device, **kw)
+        seg = StreamSegmenter(self.n, self.cfg, hops_per_step=self.K, audio_dtype=self.input_dtype,
+                              device=self.frames.device, **kw)
+        if sessions:
+            self._session_segmenters.add(seg)
+        return seg
 
     @property
     def graph_direct(self):
