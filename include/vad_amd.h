@@ -1398,6 +1398,67 @@ int vad_resample_stream_i16_i16(vad_resample_plan* plan, const int16_t* in, int6
                                 void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Sessions through the stream resampler: the converter in front of
+ * vad_stream_hops_sessions, each stream at a rate of its own.  `plans` is a
+ * HOST array of n_rates plans (1 .. VAD_RESAMPLE_MAX_RATES, all for the same
+ * output rate; each uploaded by vad_resample_plan_upload or by the first
+ * launch, as above).  Per stream the kernel reads, at the start of every call,
+ *   hop_counts[s]  int32: the stream converts n_s = min(max(count, 0), n_hops)
+ *                  hops, rows 0 .. n_s-1 of its column of `in`, into rows
+ *                  0 .. n_s-1 of its column of `out`; rows n_s .. n_hops-1 of
+ *                  `out` are NOT written (the hop kernel does not read them);
+ *   restart[s]     uint8, owned by the resampler: nonzero -> the stream's
+ *                  history and emitted count become zero, its rate becomes
+ *                  plans[min(max(rate_index[s], 0), n_rates - 1)], and the
+ *                  kernel stores 0 back (a flag set once restarts once, also
+ *                  under graph replay); only then are its hops converted;
+ *   rate_index[s]  int32, read under a nonzero flag only: a running session
+ *                  cannot change rate.
+ * A stream with n_s = 0 and no flag writes nothing, its state included.  The
+ * stream's rate picks the phase table, up, down, T, the history length,
+ * hop_in, delay and c_off; each output is the one fp32 chain of the entries
+ * above, so a session's rows equal, bit for bit, what vad_resample_stream_*
+ * writes for the same plan and input from a zero state (z[n] = 0 for the
+ * first `delay` outputs of every session).  in: element i of hop k of stream
+ * s at in[k * block_stride + s * hop_stride + i], the layouts of
+ * vad_stream_hops with a row as wide as the largest hop_in of the rates (a
+ * stream reads the first hop_in(rate) samples of its rows).  out: (n_hops,
+ * n_streams, hop_out) contiguous.  state: vad_resample_sessions_state_bytes
+ * bytes, 4-byte aligned -- per stream a history padded to the longest of the
+ * rates, the emitted count and the rate index; all zero = a fresh stream at
+ * plans[0].  One workgroup per stream up to vad_resample_sessions_grid
+ * workgroups, which loop over the streams past that; no atomics, no workgroup
+ * waits on another.
+ * VAD_EINVAL, before any HIP call: plans null or a null plan in it, n_rates
+ * outside 1 .. VAD_RESAMPLE_MAX_RATES, a negative count, hop_out <= 0,
+ * hop_out * down % up != 0 for any rate, n_hops * hop_in + history over
+ * VAD_RESAMPLE_MAX_SPAN for any rate, rows that repeat or overlap; then, with
+ * at least one stream and one hop (zero of either succeeds and does nothing):
+ * a null pointer, in / out not aligned to their sample size, state /
+ * hop_counts / rate_index not 4-byte aligned, or any two of in, out, state,
+ * hop_counts, restart, rate_index sharing a byte.
+ * ------------------------------------------------------------------------- */
+#define VAD_RESAMPLE_MAX_RATES 8
+int32_t vad_resample_sessions_grid(void);
+size_t vad_resample_sessions_state_bytes(vad_resample_plan* const* plans, int32_t n_rates, int64_t n_streams);
+int vad_resample_stream_sessions_f32_f32(vad_resample_plan* const* plans, int32_t n_rates, const float* in,
+                                         int64_t hop_stride, int64_t block_stride, int64_t n_streams, int32_t n_hops,
+                                         int32_t hop_out, const int32_t* hop_counts, uint8_t* restart,
+                                         const int32_t* rate_index, void* state, float* out, void* stream);
+int vad_resample_stream_sessions_f32_i16(vad_resample_plan* const* plans, int32_t n_rates, const float* in,
+                                         int64_t hop_stride, int64_t block_stride, int64_t n_streams, int32_t n_hops,
+                                         int32_t hop_out, const int32_t* hop_counts, uint8_t* restart,
+                                         const int32_t* rate_index, void* state, int16_t* out, void* stream);
+int vad_resample_stream_sessions_i16_f32(vad_resample_plan* const* plans, int32_t n_rates, const int16_t* in,
+                                         int64_t hop_stride, int64_t block_stride, int64_t n_streams, int32_t n_hops,
+                                         int32_t hop_out, const int32_t* hop_counts, uint8_t* restart,
+                                         const int32_t* rate_index, void* state, float* out, void* stream);
+int vad_resample_stream_sessions_i16_i16(vad_resample_plan* const* plans, int32_t n_rates, const int16_t* in,
+                                         int64_t hop_stride, int64_t block_stride, int64_t n_streams, int32_t n_hops,
+                                         int32_t hop_out, const int32_t* hop_counts, uint8_t* restart,
+                                         const int32_t* rate_index, void* state, int16_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU clip sharding: one process per GPU, each
  * classifying its shard (vad_amd/dist.py split_clip: windows [w_lo, w_hi)
  * from samples [160 w_lo, 160 (w_hi + 4) + 401)), then ONE collective: the

@@ -22,7 +22,8 @@ def __getattr__(name):
         from .simple_stream import SimpleStreamBatch
         return SimpleStreamBatch
     # the resamplers load the built library on first use
-    if name in ("Resampler", "StreamResampler", "resample_clips", "resample_model", "ResampleSpec"):
+    if name in ("Resampler", "StreamResampler", "SessionStreamResampler", "resample_clips", "resample_model",
+                "ResampleSpec"):
         from . import resample
         return getattr(resample, name)
     # the score entries load the built library on first use

@@ -241,6 +241,11 @@ SIGNATURES = {
     "vad_resample_stream_state_bytes": (c_sz, [c_vp, c_i64]),
     **{f"vad_resample_stream_{i}_{o}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp])
        for i in ("f32", "i16") for o in ("f32", "i16")},
+    "vad_resample_sessions_grid": (c_i32, []),
+    "vad_resample_sessions_state_bytes": (c_sz, [c_vp, c_i32, c_i64]),
+    **{f"vad_resample_stream_sessions_{i}_{o}": (c_int, [c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp,
+                                                         c_vp, c_vp, c_vp, c_vp, c_vp])
+       for i in ("f32", "i16") for o in ("f32", "i16")},
     "vad_rccl_available": (c_int, []),
     "vad_rccl_error_string": (ctypes.c_char_p, []),
     "vad_rccl_unique_id": (c_int, [c_vp]),

@@ -27,6 +27,17 @@
 // (Hn input samples, fp32, in device memory) followed by the K new hops as one
 // window and computes the K * hop_out outputs of the block from it; the last
 // Hn samples of the window are the next history.
+//
+// resample_stream_sessions_kernel: the stream kernel for sessions.  Per stream
+// it reads hop_counts[s] (n_s = min(max(count, 0), K) hops), a restart flag
+// (nonzero: the history and the emitted count become zero, the stream adopts
+// rate_index[s] clamped into [0, R-1], and 0 is stored back) and the stream's
+// stored rate index, which picks the phase table, T, the history length,
+// hop_in, delay and c_off of one of R plans -- uniform over the workgroup.
+// The table is staged per stream: the next stream of the workgroup may be at
+// another rate.  Rows n_s..K-1 of `out` are not written, and a stream with no
+// hop and no restart writes nothing at all.  Each output is the same
+// resample_dot chain with the same q, jl, r as resample_stream_kernel.
 #include <mutex>
 #include <vector>
 
@@ -48,6 +59,8 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kTileOut = VAD_RESAMPLE_TILE;
 constexpr int kGrid = 2048;  // 256 CUs x 8 workgroups of 4 waves
+constexpr int kSessGrid = 2048;  // workgroups of the sessions stream kernel; more streams are looped over
+constexpr int kMaxRates = VAD_RESAMPLE_MAX_RATES;
 constexpr int kMaxTable = VAD_RESAMPLE_MAX_TABLE;
 constexpr int kMaxSpan = VAD_RESAMPLE_MAX_SPAN;
 
@@ -212,6 +225,75 @@ __global__ __launch_bounds__(kThreads) void resample_stream_kernel(StreamArgs a)
   }
 }
 
+struct RateArgs {
+  Phase p;
+  int hop_in, Hn, delay, c_off;
+};
+
+struct SessArgs {
+  RateArgs r[kMaxRates];
+  int n_rates;
+  const void* in;
+  int64_t hop_stride, block_stride;
+  int64_t n_streams;
+  int n_hops, hop_out;
+  int Hmax;                    // the longest history of the rates: the stride of hist
+  const int32_t* hop_counts;   // [S]
+  uint8_t* restart;            // [S], consumed
+  const int32_t* rate_index;   // [S], read under a restart flag only
+  float* hist;                 // [S][Hmax], the first Hn(rate) of a row in use, the rest zero
+  int32_t* emitted;            // [S], min(outputs emitted, delay)
+  int32_t* rate;               // [S], the rate index the session runs at
+  void* out;                   // (K, S, hop_out)
+};
+
+template <typename TI, typename TO>
+__global__ __launch_bounds__(kThreads) void resample_stream_sessions_kernel(SessArgs a) {
+  extern __shared__ float lds[];
+  const TI* in = static_cast<const TI*>(a.in);
+  TO* out = static_cast<TO*>(a.out);
+  for (int64_t s = blockIdx.x; s < a.n_streams; s += gridDim.x) {
+    __syncthreads();  // the previous stream's table and window have been read
+    const int c = a.hop_counts[s];
+    const int n = __builtin_amdgcn_readfirstlane(c < 0 ? 0 : (c > a.n_hops ? a.n_hops : c));
+    const bool fresh = __builtin_amdgcn_readfirstlane((int)a.restart[s]) != 0;
+    if (n == 0 && !fresh) continue;  // stalled: nothing is written, the state included
+    int ri = a.rate[s];
+    if (fresh) ri = a.rate_index[s];
+    ri = __builtin_amdgcn_readfirstlane(ri < 0 ? 0 : (ri >= a.n_rates ? a.n_rates - 1 : ri));
+    const RateArgs& ra = a.r[ri];
+    const Phase& p = ra.p;
+    float* ph = lds;
+    float* w = lds + p.up * p.Ts;
+    stage_table(p, ph);
+    const int n_new = n * ra.hop_in, n_outs = n * a.hop_out;
+    float* hist = a.hist + s * a.Hmax;
+    for (int i = threadIdx.x; i < ra.Hn; i += kThreads) w[i] = fresh ? 0.f : hist[i];
+    for (int i = threadIdx.x; i < n_new; i += kThreads) {
+      const int k = i / ra.hop_in, o = i - k * ra.hop_in;
+      w[ra.Hn + i] = to_f32(in[k * a.block_stride + s * a.hop_stride + o]);
+    }
+    const int em = fresh ? 0 : a.emitted[s];
+    __syncthreads();  // every read of the flag and the state lies before it, every write after it
+    for (int e = threadIdx.x; e < n_outs; e += kThreads) {
+      const int q = e * p.down + ra.c_off;
+      const int jl = q / p.up;
+      const int r = q - jl * p.up;
+      float v = resample_dot(w + (p.T - 1) + jl, ph + r * p.Ts, p.T);
+      if (em + e < ra.delay) v = 0.f;  // z[n] = 0 for n < d, per session
+      const int k = e / a.hop_out, o = e - k * a.hop_out;
+      out[((int64_t)k * a.n_streams + s) * a.hop_out + o] = from_f32<TO>(v);
+    }
+    for (int i = threadIdx.x; i < ra.Hn; i += kThreads) hist[i] = w[n_new + i];
+    if (fresh)  // what a longer history of the last session left behind
+      for (int i = ra.Hn + threadIdx.x; i < a.Hmax; i += kThreads) hist[i] = 0.f;
+    if (threadIdx.x == 0) {
+      a.emitted[s] = em + n_outs < ra.delay ? em + n_outs : ra.delay;
+      if (fresh) a.rate[s] = ri, a.restart[s] = 0;
+    }
+  }
+}
+
 int gcd_i(int a, int b) {
   while (b) { const int t = a % b; a = b; b = t; }
   return a;
@@ -313,6 +395,78 @@ int stream_entry(vad_resample_plan* p, const void* in, int64_t hop_stride, int64
   return (int)hipGetLastError();
 }
 
+// hop_in, history, delay and c_off of a plan for hops of hop_out outputs; false when a hop is no whole
+// number of input samples or K hops and the history pass the LDS window
+bool rate_args(const vad_resample_plan* p, int32_t n_hops, int32_t hop_out, RateArgs* r) {
+  if ((int64_t)hop_out * p->down % p->up) return false;
+  const int64_t hop_in = (int64_t)hop_out * p->down / p->up;
+  const int Hn = history_len(p);
+  if (hop_in <= 0 || (int64_t)n_hops * hop_in + Hn > kMaxSpan || (int64_t)n_hops * hop_out > INT32_MAX / p->down - 1)
+    return false;
+  const int c0 = p->delay * p->down - p->P, Hc = (c0 + p->up - 1) / p->up;
+  r->hop_in = (int)hop_in, r->Hn = Hn, r->delay = p->delay, r->c_off = Hc * p->up - c0;
+  return true;
+}
+
+template <typename TI, typename TO>
+int sessions_entry(vad_resample_plan* const* plans, int32_t n_rates, const void* in, int64_t hop_stride,
+                   int64_t block_stride, int64_t n_streams, int32_t n_hops, int32_t hop_out, const int32_t* hop_counts,
+                   uint8_t* restart, const int32_t* rate_index, void* state, void* out, void* stream) {
+  if (!plans || n_rates < 1 || n_rates > kMaxRates) return VAD_EINVAL;
+  if (n_streams < 0 || n_hops < 0 || hop_out <= 0 || n_streams > INT32_MAX) return VAD_EINVAL;
+  SessArgs a{};
+  int64_t hop_in = 0;  // the widest of the rates: the width of an input row
+  int lds = 0;
+  for (int i = 0; i < n_rates; ++i) {
+    const vad_resample_plan* p = plans[i];
+    if (!p || !rate_args(p, n_hops, hop_out, &a.r[i])) return VAD_EINVAL;
+    hop_in = a.r[i].hop_in > hop_in ? a.r[i].hop_in : hop_in;
+    a.Hmax = a.r[i].Hn > a.Hmax ? a.r[i].Hn : a.Hmax;
+    const int need = p->up * p->Ts + a.r[i].Hn + n_hops * a.r[i].hop_in;
+    lds = need > lds ? need : lds;
+  }
+  if (hop_stride < hop_in) return VAD_EINVAL;
+  if (n_hops > 1 && !(block_stride > 0 &&
+                      (block_stride >= (n_streams - 1) * hop_stride + hop_in ||
+                       (block_stride >= hop_in && hop_stride >= (n_hops - 1) * block_stride + hop_in))))
+    return VAD_EINVAL;  // the hop-major or stream-major blocks of vad_stream_hops
+  if (n_streams == 0 || n_hops == 0) return VAD_OK;
+  if (!in || !state || !out || !hop_counts || !restart || !rate_index) return VAD_EINVAL;
+  if (reinterpret_cast<uintptr_t>(in) % sizeof(TI) || reinterpret_cast<uintptr_t>(out) % sizeof(TO) ||
+      reinterpret_cast<uintptr_t>(state) % 4 || reinterpret_cast<uintptr_t>(hop_counts) % 4 ||
+      reinterpret_cast<uintptr_t>(rate_index) % 4)
+    return VAD_EINVAL;
+  const size_t in_elems = (size_t)((n_hops - 1) * (n_hops > 1 ? block_stride : 0) + (n_streams - 1) * hop_stride + hop_in);
+  const void* ptrs[6] = {in, out, state, hop_counts, restart, rate_index};
+  const size_t bytes[6] = {in_elems * sizeof(TI), (size_t)n_hops * n_streams * hop_out * sizeof(TO),
+                           (size_t)n_streams * (a.Hmax + 2) * 4, (size_t)n_streams * 4, (size_t)n_streams,
+                           (size_t)n_streams * 4};
+  for (int i = 0; i < 6; ++i)
+    for (int j = i + 1; j < 6; ++j)
+      if (overlap(ptrs[i], bytes[i], ptrs[j], bytes[j])) return VAD_EINVAL;
+  for (int i = 0; i < n_rates; ++i) {
+    const int rc = plan_upload(plans[i]);
+    if (rc != VAD_OK) return rc;
+    a.r[i].p = phase_of(plans[i]);
+  }
+  a.n_rates = n_rates;
+  a.in = in, a.hop_stride = hop_stride, a.block_stride = n_hops > 1 ? block_stride : 0, a.n_streams = n_streams;
+  a.n_hops = n_hops, a.hop_out = hop_out;
+  a.hop_counts = hop_counts, a.restart = restart, a.rate_index = rate_index;
+  a.hist = static_cast<float*>(state);
+  a.emitted = reinterpret_cast<int32_t*>(a.hist + n_streams * a.Hmax);
+  a.rate = a.emitted + n_streams;
+  a.out = out;
+  static std::atomic<unsigned long long> done{0};
+  const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&resample_stream_sessions_kernel<TI, TO>),
+                                      (kMaxTable + kMaxSpan) * (int)sizeof(float), done);
+  if (e != hipSuccess) return (int)e;
+  resample_stream_sessions_kernel<TI, TO><<<dim3((unsigned)(n_streams < kSessGrid ? n_streams : kSessGrid)),
+                                            dim3(kThreads), lds * (int)sizeof(float),
+                                            static_cast<hipStream_t>(stream)>>>(a);
+  return (int)hipGetLastError();
+}
+
 }  // namespace
 }  // namespace vad
 
@@ -363,6 +517,19 @@ size_t vad_resample_stream_state_bytes(const vad_resample_plan* p, int64_t n_str
   return (size_t)n_streams * (size_t)(history_len(p) + 1) * 4;
 }
 
+int32_t vad_resample_sessions_grid(void) { return kSessGrid; }
+
+size_t vad_resample_sessions_state_bytes(vad_resample_plan* const* plans, int32_t n_rates, int64_t n_streams) {
+  if (!plans || n_rates < 1 || n_rates > kMaxRates || n_streams <= 0 || n_streams > INT32_MAX) return 0;
+  int Hmax = 0;
+  for (int i = 0; i < n_rates; ++i) {
+    if (!plans[i]) return 0;
+    const int Hn = history_len(plans[i]);
+    Hmax = Hn > Hmax ? Hn : Hmax;
+  }
+  return (size_t)n_streams * (size_t)(Hmax + 2) * 4;
+}
+
 #define VAD_RESAMPLE_ENTRIES(IN, TI, OUT, TO)                                                                        \
   int vad_resample_batch_##IN##_##OUT(vad_resample_plan* p, const int64_t* src_ptrs, const int64_t* lens_in,        \
                                       const int64_t* start, int64_t n_clips, TO* dst, int64_t total, void* stream) { \
@@ -372,6 +539,14 @@ size_t vad_resample_stream_state_bytes(const vad_resample_plan* p, int64_t n_str
                                        int64_t n_streams, int32_t n_hops, int32_t hop_out, void* state, TO* out,     \
                                        void* stream) {                                                               \
     return stream_entry<TI, TO>(p, in, hop_stride, block_stride, n_streams, n_hops, hop_out, state, out, stream);    \
+  }                                                                                                                  \
+  int vad_resample_stream_sessions_##IN##_##OUT(vad_resample_plan* const* plans, int32_t n_rates, const TI* in,      \
+                                                int64_t hop_stride, int64_t block_stride, int64_t n_streams,         \
+                                                int32_t n_hops, int32_t hop_out, const int32_t* hop_counts,          \
+                                                uint8_t* restart, const int32_t* rate_index, void* state, TO* out,   \
+                                                void* stream) {                                                      \
+    return sessions_entry<TI, TO>(plans, n_rates, in, hop_stride, block_stride, n_streams, n_hops, hop_out,          \
+                                  hop_counts, restart, rate_index, state, out, stream);                              \
   }
 
 VAD_RESAMPLE_ENTRIES(f32, float, f32, float)

@@ -5,7 +5,8 @@ The mel bank, the 400 / 160 framing and every trained classifier assume
 ``cfg.sample_rate`` (16 kHz).  ``Resampler`` converts finished clips (one, or
 a batch written straight into the ``ClipBatch`` layout), ``StreamResampler``
 converts live streams hop by hop in front of ``StreamBatch`` /
-``SimpleStreamBatch``.
+``SimpleStreamBatch``, ``SessionStreamResampler`` does so in front of a
+sessions batch, each stream at the rate its session started with.
 
 Definition.  For rate_in -> rate_out, g = gcd, up = rate_out / g, down =
 rate_in / g, P = 10 * max(up, down); ``taps`` are the 2P+1 taps of
@@ -33,6 +34,8 @@ from .config import MfccConfig
 TILE_OUT = 1024     # outputs per destination tile (VAD_RESAMPLE_TILE)
 MAX_TABLE = 16384   # floats of the phase table in LDS (VAD_RESAMPLE_MAX_TABLE)
 MAX_SPAN = 16384    # floats of the input tile / stream window in LDS (VAD_RESAMPLE_MAX_SPAN)
+MAX_RATES = 8       # rates of one SessionStreamResampler (VAD_RESAMPLE_MAX_RATES)
+SESSIONS_GRID = 2048  # workgroups of the sessions stream kernel (vad_resample_sessions_grid)
 
 
 def design_taps(up, down):
@@ -459,3 +462,176 @@ class StreamResampler:
             return self.out.new_zeros((self.n, 0))
         z = torch.cat(got).transpose(0, 1).reshape(self.n, -1)
         return z[:, :d].contiguous()
+
+
+class SessionStreamResampler:
+    """The stream resampler for sessions: S slots whose callers join, hang up
+    and stall, each session at a rate of its own out of ``rates`` (1 ..
+    MAX_RATES distinct rates, multiples of 100 Hz; cfg.sample_rate itself is
+    the copy, with delay 0).  One launch converts, per stream, the first
+    n_s = min(max(hop_counts[s], 0), K) hops of its column of ``inputs``
+    (K, S, hop_in_max) -- the first ``hop_ins[i]`` samples of a row for a
+    stream at rates[i] -- into rows 0..n_s-1 of its column of ``out`` (K, S,
+    cfg.hop); rows n_s..K-1 are not written.  Static device tensors, read at
+    the start of every step:
+
+      hop_counts (S,) int32   shared with the hop kernel when given (neither
+                              kernel writes it); K by default
+      restart    (S,) uint8   the resampler's own: nonzero makes the stream
+                              fresh (zero history, the first ``delays[i]``
+                              outputs zero again) at rates[rate_index[s]],
+                              and the kernel stores 0 back
+      rate_index (S,) int32   read under a flag only, clamped into the rates
+      state                   histories padded to the longest, emitted
+                              counts, the rate index of every stream
+
+    A stream with no hop and no flag keeps every byte of its state.  A
+    session's rows are, bit for bit, those of a freshly reset StreamResampler
+    of its rate fed the same hops.  Built by ``StreamBatch.resampler`` it
+    writes the batch's ``inputs`` and shares its ``hop_counts``, and
+    ``restart=`` reaches batch, resampler and session segmenters alike."""
+
+    def __init__(self, n_streams, rates, cfg: MfccConfig = MfccConfig(), hops_per_step=1, input_dtype=None,
+                 out=None, hop_counts=None, out_dtype=None, device=None, batch=None):
+        import torch
+        from . import _lib
+        rates = [rates] if np.ndim(rates) == 0 else list(rates)
+        if not 1 <= len(rates) <= MAX_RATES:
+            raise ValueError(f"1 to {MAX_RATES} rates, got {len(rates)}")
+        for r in rates:
+            if int(r) != r or r <= 0:
+                raise ValueError(f"sample rates are positive integers, got {r}")
+            if int(r) % 100:
+                raise ValueError(f"streams take rates that are multiples of 100 Hz, got {r}")
+        self.rates = [int(r) for r in rates]
+        if len(set(self.rates)) != len(self.rates):
+            raise ValueError(f"the rates are distinct, got {self.rates}")
+        self.specs = [ResampleSpec(r, cfg.sample_rate) for r in self.rates]
+        self.cfg, self.n, self.K = cfg, int(n_streams), int(hops_per_step)
+        if self.n < 1 or self.K < 1:
+            raise ValueError("n_streams and hops_per_step must be >= 1")
+        self.hop_out = int(cfg.hop)
+        for s in self.specs:
+            if cfg.hop * s.down % s.up:
+                raise ValueError(f"a hop of {cfg.hop} samples at {cfg.sample_rate} Hz is no whole number of samples "
+                                 f"at {s.rate_in} Hz")
+        self.hop_ins = [cfg.hop * s.down // s.up for s in self.specs]
+        for s, h in zip(self.specs, self.hop_ins):
+            if self.K * h + s.history > MAX_SPAN:
+                raise ValueError(f"{self.K} hops of {h} samples and the history ({s.history}) exceed the "
+                                 f"{MAX_SPAN}-float window")
+        self.hop_in = max(self.hop_ins)
+        self.delays = [s.delay for s in self.specs]
+        self.input_dtype = torch.float32 if input_dtype is None else input_dtype
+        iname = _tname(self.input_dtype)
+        if out is not None:
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous()
+                    and tuple(out.shape) == (self.K, self.n, self.hop_out)):
+                raise ValueError(f"out must be a contiguous CUDA tensor of shape {(self.K, self.n, self.hop_out)}")
+            if out_dtype is not None and out_dtype != out.dtype:
+                raise ValueError("out_dtype differs from out's")
+            dev = out.device
+        else:
+            dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+            out = torch.zeros((self.K, self.n, self.hop_out), dtype=out_dtype or torch.float32, device=dev)
+        self.out = out
+        if hop_counts is None:
+            hop_counts = torch.full((self.n,), self.K, dtype=torch.int32, device=dev)
+        elif not (isinstance(hop_counts, torch.Tensor) and hop_counts.is_cuda and hop_counts.is_contiguous()
+                  and tuple(hop_counts.shape) == (self.n,) and hop_counts.dtype == torch.int32):
+            raise ValueError(f"hop_counts must be a contiguous CUDA int32 tensor of shape ({self.n},)")
+        self.hop_counts = hop_counts
+        self._batch = batch
+        self.plans = [_plan(s, dev) for s in self.specs]
+        self._handles = (ctypes.c_void_p * len(self.plans))(*[p.handle.value for p in self.plans])
+        lib = _lib.lib()
+        assert lib.vad_resample_sessions_grid() == SESSIONS_GRID
+        self._name = f"vad_resample_stream_sessions_{iname}_{_tname(out.dtype)}"
+        self._fn = getattr(lib, self._name)
+        nbytes = int(lib.vad_resample_sessions_state_bytes(self._handles, len(self.plans), self.n))
+        self.state = torch.zeros((nbytes // 4,), dtype=torch.int32, device=dev)
+        self.inputs = torch.zeros((self.K, self.n, self.hop_in), dtype=self.input_dtype, device=dev)
+        self.restart = torch.ones((self.n,), dtype=torch.uint8, device=dev)  # the first step adopts rate_index
+        self.rate_index = torch.zeros((self.n,), dtype=torch.int32, device=dev)
+        self.graph = None
+
+    @property
+    def history(self):
+        """(S, longest history) float32 view of the state's histories."""
+        import torch
+        h = max(s.history for s in self.specs)
+        return self.state[:self.n * h].view(torch.float32).view(self.n, h)
+
+    @property
+    def emitted(self):
+        """(S,) int32: min(outputs emitted by the session, its delay)."""
+        return self.state[self.state.numel() - 2 * self.n:self.state.numel() - self.n]
+
+    @property
+    def stream_rate(self):
+        """(S,) int32: the index in ``rates`` every stream's session runs at."""
+        return self.state[self.state.numel() - self.n:]
+
+    def reset(self):
+        """Every stream fresh; the next step adopts ``rate_index``."""
+        self.state.zero_()
+        self.restart.fill_(1)
+
+    def _launch(self, stream=None):
+        from . import _lib
+        x = self.inputs
+        rc = self._fn(self._handles, len(self.plans), _lib.ptr(x), x.stride(1), x.stride(0), self.n, self.K,
+                      self.hop_out, _lib.ptr(self.hop_counts), _lib.ptr(self.restart), _lib.ptr(self.rate_index),
+                      _lib.ptr(self.state), _lib.ptr(self.out), _lib.stream_ptr() if stream is None else stream)
+        if rc:
+            _lib.check(rc, self._name)
+
+    def _set(self, t, dst, name):
+        import torch
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.shape != dst.shape or t.dtype != dst.dtype:
+            raise ValueError(f"{name} must be a CUDA {str(dst.dtype).replace('torch.', '')} tensor of shape "
+                             f"{tuple(dst.shape)}")
+        dst.copy_(t)
+
+    def step_block(self, x=None, hop_counts=None, restart=None, rate=None):
+        """One step.  x (K, S, hop_in) of the input dtype, hop_counts (S,)
+        int32, restart (S,) uint8 and rate (S,) int32 -- indices into
+        ``rates`` -- are CUDA tensors copied into ``inputs``, ``hop_counts``,
+        ``restart`` and ``rate_index``; None leaves those as written.  Behind
+        a StreamBatch, hop_counts and restart go through the batch, so the
+        hop kernel and the session segmenters see them too.  Returns ``out``."""
+        if rate is not None:
+            self._set(rate, self.rate_index, "rate")
+        if self._batch is not None:
+            self._batch._set_sessions(hop_counts, restart)
+        else:
+            if hop_counts is not None:
+                self._set(hop_counts, self.hop_counts, "hop_counts")
+            if restart is not None:
+                self._set(restart, self.restart, "restart")
+        if x is not None:
+            self._set(x, self.inputs, "x")
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._launch()
+        return self.out
+
+    def capture(self):
+        """Capture one step into a graph; step_block replays it.  The warm-up
+        launch consumes restart flags and advances the streams: state, out
+        and flags are put back after it."""
+        import torch
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        saved = (self.state.clone(), self.out.clone(), self.restart.clone())
+        with torch.cuda.stream(s):
+            self._launch()  # warm-up (first launch sets kernel attributes)
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        self.state.copy_(saved[0]); self.out.copy_(saved[1]); self.restart.copy_(saved[2])
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._launch()
+        self.graph = g
+        return g

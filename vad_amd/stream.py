@@ -99,11 +99,19 @@ because the hop kernel has cleared the batch's by the time the segmenter
 runs; step / step_block copy a ``restart=`` they are given into it as well, so
 ``sb.step_block(x, hop_counts=c, restart=r); seg.push(sb.label_block,
 sb.inputs)`` is the whole loop.  A caller that writes ``sb.restart`` directly
-(for a replayed graph) writes ``seg.restart`` too.  Not covered:
+(for a replayed graph) writes ``seg.restart`` too.  resampler(rates) returns
+a SessionStreamResampler (vad_amd.resample) in front: callers at 8, 44.1 or
+48 kHz, each session at the rate it started with.  It writes ``inputs``,
+reads this batch's ``hop_counts`` and owns a third ``restart`` (and a
+``rate_index`` read under that flag only), so
+``rs.step_block(x, hop_counts=c, restart=r, rate=i); sb.step_block();
+seg.push(sb.label_block, sb.inputs)`` is the whole loop with callers at their
+own rates, a slot reused by a caller at another rate included.  Not covered:
 kernel="three"; segmenter() without sessions=True (the plain online segmenter
-counts one window per label row); feeding the segmenter from step_host /
-HostPipeline (the caller copies ``host_restart`` into ``seg.restart`` itself);
-a StreamResampler in front.
+counts one window per label row); feeding the segmenter or the resampler from
+step_host / HostPipeline (the caller copies ``host_restart`` into
+``seg.restart`` itself); the last ``delay`` output samples of a session that
+ends behind a resampler (under 1.3 ms).
 
 Blocks in flight: host_pipeline(depth) returns a HostPipeline with `depth`
 slots, each with pinned host buffers and a device input / label block of its
@@ -240,6 +248,7 @@ class StreamBatch:
         self.host_inputs = None
         self.host_labels = None
         self._session_segmenters = weakref.WeakSet()  # segmenter(sessions=True): handed restart= by _set_sessions
+        self._session_resamplers = weakref.WeakSet()  # resampler(rates): the same
         self.host_hop_counts = None
         self.host_restart = None
 
@@ -322,6 +331,8 @@ class StreamBatch:
             self.restart.copy_(restart)
             for seg in self._session_segmenters:  # each consumes a flag of its own
                 seg.restart.copy_(restart)
+            for rs in self._session_resamplers:
+                rs.restart.copy_(restart)
 
     def _hop_call(self, h, n_hops=1, labels=None, stream=None, sess=None):
         """vad_stream_hops (_i16 for an int16 batch) with the per-batch
@@ -568,6 +579,25 @@ class StreamBatch:
         if sessions:
             self._session_segmenters.add(seg)
         return seg
+
+    def resampler(self, rates, **kw):
+        """A SessionStreamResampler (vad_amd.resample) in front of this
+        sessions batch: its ``out`` is the batch's ``inputs``, its
+        ``hop_counts`` the batch's tensor, and a ``restart=`` given to either's
+        step is copied into the batch's, the resampler's and the session
+        segmenters' flags (the batch holds the resampler weakly).  kw:
+        input_dtype (of the callers' audio; the batch's input dtype is the
+        resampler's output)."""
+        from .resample import SessionStreamResampler
+        if self.kernel == "three":
+            raise ValueError("resampler(): sessions live in the one-kernel hop, kernel='three' has none")
+        if not self.sessions:
+            raise ValueError("resampler(): build the batch with sessions=True (a batch without sessions takes a "
+                             "StreamResampler with out=inputs)")
+        rs = SessionStreamResampler(self.n, rates, self.cfg, hops_per_step=self.K, out=self.inputs,
+                                    hop_counts=self.hop_counts, batch=self, **kw)
+        self._session_resamplers.add(rs)
+        return rs
 
     @property
     def graph_direct(self):
