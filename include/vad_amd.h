@@ -627,6 +627,25 @@ int vad_stream_step_tree(const vad_mfcc_plan* plan, const vad_tree_plan* tree, c
                          uint8_t* labels, float* mfcc_scratch, void* stream);
 /* largest table the hop kernel walks from LDS; -1 on a bad plan */
 int64_t vad_stream_tree_max_lds_nodes(const vad_mfcc_plan* plan);
+/* The block shape of a hop launch, as a read-only query (no device work; the
+ * launchers of every vad_stream_hops* entry call the same rule).  A block
+ * holds 1, 2, 4, 8 or 16 waves, one stream each: at least 4 for a one-hop
+ * launch and 1 for n_hops > 1, doubled while there are more streams than
+ * waves x compute units of the current device (256 when none answers), then
+ * halved while the staged tables and the waves' scratch exceed 160 KiB.
+ *   vad_stream_hop_table_bytes       the bytes an FFN launch stages per block
+ *                                    (the plan's hop tables and the weights);
+ *   vad_stream_hop_tree_table_bytes  the same for a tree launch with `walk`
+ *                                    (the hop tables, and the 16-B nodes when
+ *                                    they are walked from LDS);
+ *   vad_stream_hop_block_waves       waves per block for those bytes, or 0
+ *                                    for n_streams == 0 or n_hops == 0 (the
+ *                                    entries return before any launch).
+ * Refusals: VAD_EINVAL for a null or table-less plan, any other `walk`, a
+ * negative argument, and table_bytes that leave no room for one wave. */
+int64_t vad_stream_hop_table_bytes(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn);
+int64_t vad_stream_hop_tree_table_bytes(const vad_mfcc_plan* plan, const vad_tree_plan* tree, int32_t walk);
+int32_t vad_stream_hop_block_waves(int64_t table_bytes, int64_t n_streams, int32_t n_hops);
 
 /* Scored hops: the operating point on the live path.  Each entry is the label
  * entry of the same name plus `active`, `scores` and `score_block_stride`:

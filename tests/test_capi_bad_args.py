@@ -54,6 +54,13 @@ call("vad_stream_push_hop", N, 400, 400, N, 160, 500, 10, N)
 call("vad_stream_hop", N, N, N, 400, 400, N, 160, 160, 10, N, N, N, N)
 call("vad_stream_hops", N, N, N, 400, 400, N, 160, 160, 10, 8, 1600, N, N, N, 10, N)
 call("vad_stream_step", N, N, N, 400, 400, 10, N, N, N, N, N)
+call("vad_stream_hop_table_bytes", N, N)
+call("vad_stream_hop_tree_table_bytes", N, N, 0)
+call("vad_stream_hop_tree_table_bytes", N, N, 2)
+call("vad_stream_hop_block_waves", -1, 10, 1)
+call("vad_stream_hop_block_waves", 30000, -1, 1)
+call("vad_stream_hop_block_waves", 30000, 10, -1)
+call("vad_stream_hop_block_waves", 160 * 1024, 10, 1)  # no room for one wave's scratch
 call("vad_graph_launch", N, N)
 call("vad_graph_plan_create", N, N, N)
 call("vad_graph_plan_launch", N, N)
@@ -71,6 +78,8 @@ neutral = {
     "vad_n_frames_neg": int(L.vad_n_frames(-5, 400, 160)),
     "vad_stream_ring_floats_neg": int(L.vad_stream_ring_floats(-1, 13)),
     "vad_format_csv_rows_null": int(L.vad_format_csv_rows(N, 3, 39, 1.0, N, 100)),
+    "vad_stream_hop_block_waves_none": [int(L.vad_stream_hop_block_waves(30000, 0, 1)),
+                                        int(L.vad_stream_hop_block_waves(30000, 10, 0))],
 }
 print(json.dumps({"calls": res, "neutral": neutral}))
 '''
@@ -92,3 +101,4 @@ def test_every_entry_refuses_bad_arguments():
     assert n["vad_n_frames_neg"] == 0
     assert n["vad_stream_ring_floats_neg"] <= 0
     assert n["vad_format_csv_rows_null"] < 0
+    assert n["vad_stream_hop_block_waves_none"] == [0, 0]  # no streams or no hops: no launch, no block

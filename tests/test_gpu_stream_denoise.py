@@ -15,8 +15,8 @@ import pytest
 from oracle import vad_oracle as O
 
 import stream_denoise_reference as D
-from test_gpu_stream_scores import (L, H, audio, batch, clip_chain_device, cuda, ffn, packed, poison,  # noqa: F401
-                                    torch_cuda, tree_with_scores)
+from test_gpu_stream_scores import (L, H, audio, batch, clip_chain_device, cuda, ffn, framing, is_16_chunk,  # noqa: F401
+                                    packed, poison, torch_cuda, tree_with_scores)
 
 pytestmark = pytest.mark.gpu
 
@@ -64,7 +64,7 @@ def clf_for(name):
     return tree_with_scores() if name == "tree" else ffn(name)
 
 
-def noise_frames(S, n, seed=77, dtype=np.float32):
+def noise_frames(S, n, seed=77, dtype=np.float32, L=L):
     """n frames per stream of a noise floor: integer-valued Gaussian noise."""
     rng = np.random.default_rng(seed)
     return np.rint(rng.normal(0.0, 300.0, size=(S, n, L))).astype(dtype)
@@ -135,19 +135,19 @@ def test_silence_under_a_loaded_noise_floor(torch_cuda, name, dtype):
 # ---------------------------------------------------------------------------
 # 3. bookkeeping, 4. the estimate, and the records 5. reads
 # ---------------------------------------------------------------------------
-def run_recorded(torch, clf, S, T, noise_class, loaded_n, alpha=0.9, dtype="float32", update=True, **kw):
+def run_recorded(torch, clf, S, T, noise_class, loaded_n, alpha=0.9, dtype="float32", update=True, L=L, H=H, **kw):
     """K = 1 hops with everything recorded per hop: labels, the raw spectrum
     row of the hop's frame, the estimate in force BEFORE the hop, the frame,
     the new MFCC ring row; the device's rows / count / estimate are checked
     against the host replay and the fp32 model after every hop."""
     dt = getattr(torch, dtype)
-    carry, hops = audio(S, T)
+    carry, hops = audio(S, T, L=L, H=H)
     dh = cuda(hops).to(dt)
     sb = batch(torch, S, clf, carry, input_dtype=dt, denoise=True, alpha=alpha, noise_class=noise_class,
-               noise_update=update, **kw)
+               noise_update=update, cfg=framing(L, H), **kw)
     loaded = np.zeros((S, 0, D.BINS), np.float32)
     if loaded_n:
-        sb.load_noise(cuda(noise_frames(S, loaded_n)).to(dt))
+        sb.load_noise(cuda(noise_frames(S, loaded_n, L=L)).to(dt))
         loaded = sb._noise[:, :loaded_n].cpu().numpy()
         assert (sb.noise_count == loaded_n).all() and not sb._noise[:, loaded_n:].any()
     rec = dict(lab=[], spec=[], est=[], frame=[], row=[])
@@ -203,15 +203,48 @@ def test_bookkeeping_and_estimate(torch_cuda, case):
     assert not any(getattr(sb, k).any() for k in STATE) and (sb.label_block == 255).all()
 
 
+FRAMINGS_16 = [(512, 160), (1000, 333)]  # frames past 448 samples: the 16-chunk builds
+
+
+@pytest.mark.parametrize("dtype", ["float32", "int16"])
+@pytest.mark.parametrize("case", ["real_bl13", "real_tree"])
+@pytest.mark.parametrize("L16,H16", FRAMINGS_16)
+def test_bookkeeping_and_estimate_16_chunk_builds(torch_cuda, L16, H16, case, dtype):
+    """run_recorded's checks (rows, count and estimate against the host replay
+    and the fp32 model after every hop) in the 16-chunk builds."""
+    torch = torch_cuda
+    if case == "real_bl13":
+        sb, rec, pushes, _ = run_recorded(torch, ffn("bl13"), 9, 40, 0, 0, dtype=dtype, L=L16, H=H16, scores=True)
+    else:
+        sb, rec, pushes, _ = run_recorded(torch, tree_with_scores(), 5, 40, 1, 1, dtype=dtype, L=L16, H=H16)
+    assert pushes > 0 and (rec["cnt"][:, -1] > 0).any()  # noise rows were pushed: there was bookkeeping to check
+    assert is_16_chunk(sb) and sb._hop_name == ("vad_stream_hops_tree" if case == "real_tree" else "vad_stream_hops") \
+        + "_denoise" + ("_i16" if dtype == "int16" else "")
+
+
 @pytest.mark.parametrize("dtype", ["float32", "int16"])
 @pytest.mark.parametrize("n", [1, 3, 5])
 def test_load_noise(torch_cuda, n, dtype):
     """The loaded rows are the rows a hop stores for the same frames, the
     estimate is the fp32 model's, bit for bit; the properties' units."""
-    torch = torch_cuda
-    S, dt = 9, getattr(torch_cuda, dtype)
-    fr = noise_frames(S, n, seed=n)
-    sb = batch(torch, S, ffn("bl13"), fr[:, 0, H:], input_dtype=dt, denoise=True, noise_update=False)
+    load_noise_checks(torch_cuda, n, dtype)
+
+
+@pytest.mark.parametrize("dtype", ["float32", "int16"])
+@pytest.mark.parametrize("n", [1, 3, 5])
+@pytest.mark.parametrize("L16,H16", FRAMINGS_16)
+def test_load_noise_16_chunk_builds(torch_cuda, L16, H16, n, dtype):
+    """test_load_noise at frames of 512 and of 1000 samples: the second is
+    longer than the 512-point transform, which sees the first 512 samples in
+    the load kernel and in the hop kernel alike."""
+    assert is_16_chunk(load_noise_checks(torch_cuda, n, dtype, L16, H16))
+
+
+def load_noise_checks(torch, n, dtype, L=L, H=H):
+    S, dt = 9, getattr(torch, dtype)
+    fr = noise_frames(S, n, seed=n, L=L)
+    kw = dict(input_dtype=dt, denoise=True, noise_update=False, cfg=framing(L, H))
+    sb = batch(torch, S, ffn("bl13"), fr[:, 0, H:], **kw)
     sb._noise.fill_(-1.0)
     sb.load_noise(cuda(fr).to(dt))
     rows = sb._noise.cpu().numpy()
@@ -222,10 +255,17 @@ def test_load_noise(torch_cuda, n, dtype):
     assert np.array_equal(sb.noise_estimate.cpu().numpy(), sb._est.cpu().numpy() * np.float32(UNITS))
     assert np.array_equal(sb.noise_rows.cpu().numpy(), rows * np.float32(UNITS))
     # frame 0 again through a hop (the carry is its tail, the hop its last H samples after a shift by H)
-    probe = batch(torch, S, ffn("bl13"), fr[:, 0, :L - H], input_dtype=dt, denoise=True, noise_update=False)
+    probe = batch(torch, S, ffn("bl13"), fr[:, 0, :L - H], **kw)
     probe.step(cuda(np.ascontiguousarray(fr[:, 0, L - H:])).to(dt))
     assert np.array_equal(probe.frames.cpu().numpy(), fr[:, 0].astype(np.float32))
     assert same(probe._spec[:, 0], sb._noise[:, 0])
+    if L > 512:  # and samples past the transform's 512 change nothing
+        cut = fr.copy()
+        cut[:, :, 512:] = 0
+        sb2 = batch(torch, S, ffn("bl13"), fr[:, 0, H:], **kw)
+        sb2.load_noise(cuda(cut).to(dt))
+        assert same(sb2._noise[:, :n], sb._noise[:, :n]) and same(sb2._est, sb._est)
+    return probe
 
 
 # ---------------------------------------------------------------------------
@@ -237,20 +277,31 @@ def test_subtracted_rows_against_the_oracle(torch_cuda):
     against the device's ring row.  Yardstick: the zero-noise batch's rows (the
     plain batch's, bit for bit) against get_mfcc_from_spec(p) of its own
     recorded p.  Bound: twice the yardstick plus 8 * 2^-24 * max|row|."""
-    torch = torch_cuda
+    subtracted_rows_checks(torch_cuda)
+
+
+@pytest.mark.parametrize("L16,H16", FRAMINGS_16)
+def test_subtracted_rows_against_the_oracle_16_chunk_builds(torch_cuda, L16, H16):
+    """The same comparisons under the same bounds in the 16-chunk build; the
+    oracle's spectrum is given the frame as the transform sees it, its first
+    512 samples."""
+    assert is_16_chunk(subtracted_rows_checks(torch_cuda, L16, H16))
+
+
+def subtracted_rows_checks(torch, L=L, H=H):
     S, T = 5, 40
     fb = O.get_mel_filterbanks(300, 8000, 512, 26, 16000)
-    sb, rec, pushes, _ = run_recorded(torch, ffn("bl13"), S, T, 0, 5)
+    sb, rec, pushes, _ = run_recorded(torch, ffn("bl13"), S, T, 0, 5, L=L, H=H)
     assert pushes > 0 and (rec["est"] > 0).any()
     p, e = rec["spec"].astype(np.float64) * UNITS, rec["est"].astype(np.float64) * UNITS
     sub = np.maximum(p - e, 0.0)
     assert (sub == 0).any() and (sub > 0).any()  # both sides of the clamp
     want = O.get_mfcc_from_spec(sub.reshape(-1, 256), fb).reshape(S, T, -1)
     err = np.abs(rec["row"].astype(np.float64) - want).max()
-    zb, zrec, _, _ = run_recorded(torch, ffn("bl13"), S, T, 0, 0, update=False)
-    plain = batch(torch, S, ffn("bl13"), audio(S, T)[0])
+    zb, zrec, _, _ = run_recorded(torch, ffn("bl13"), S, T, 0, 0, update=False, L=L, H=H)
+    plain = batch(torch, S, ffn("bl13"), audio(S, T, L=L, H=H)[0], cfg=framing(L, H))
     for t in range(T):
-        plain.step(cuda(audio(S, T)[1][t]))
+        plain.step(cuda(audio(S, T, L=L, H=H)[1][t]))
     assert same(plain.ring, zb.ring)
     zwant = O.get_mfcc_from_spec((zrec["spec"].astype(np.float64) * UNITS).reshape(-1, 256), fb).reshape(S, T, -1)
     yard = np.abs(zrec["row"].astype(np.float64) - zwant).max()
@@ -261,7 +312,7 @@ def test_subtracted_rows_against_the_oracle(torch_cuda):
     # a recorded spectrum row against the oracle's get_spec_mag of the recorded frame, both against float64.
     # The audio spans eight decades of power, so each row's error is taken relative to the row's largest bin;
     # yardstick: numpy's FFT of the float32 frame (complex64 in NumPy 2, as the oracle notes); margin: two.
-    fr = rec["frame"].reshape(-1, L)
+    fr = rec["frame"].reshape(-1, L)[:, :512]  # what the 512-point transform sees of a longer frame
     ref = np.abs(np.fft.fft(fr.astype(np.float64), 512)[:, :256] / 512.0) ** 2
     live = ref.max(axis=1) > 0
     npy = np.stack([O.get_spec_mag(f) for f in fr]).astype(np.float64)
@@ -272,6 +323,7 @@ def test_subtracted_rows_against_the_oracle(torch_cuda):
           f"numpy float32 FFT yardstick {s_yard:.3e} = {s_yard * 2 ** 24:.2f} * 2^-24")
     assert s_err <= 2 * s_yard
     assert np.abs(rec["row"] - zrec["row"]).max() > 0.1  # and the subtraction does something
+    return sb
 
 
 # ---------------------------------------------------------------------------

@@ -20,7 +20,18 @@ from test_stream_segments_cpu import stream_audio
 
 pytestmark = pytest.mark.gpu
 
-L, H = 400, 160
+L, H = 400, 160  # the reference's framing; the helpers take another as L=, H=
+
+
+def framing(L, H):
+    from vad_amd.config import MfccConfig
+    return MfccConfig(frame_size=L, hop=H)
+
+
+def is_16_chunk(sb):
+    """The launcher's rule: a frame past 7 chunks of 64 samples takes the
+    16-chunk build of its hop kernel (launch_hop_kernels)."""
+    return sb.cfg.frame_size > 7 * 64
 
 
 @pytest.fixture(scope="module")
@@ -38,7 +49,7 @@ def cuda(x):
 # ---------------------------------------------------------------------------
 # the segmenter
 # ---------------------------------------------------------------------------
-def clip_chain_device(torch, x, clip, g, m, pad, on, off, active=1):
+def clip_chain_device(torch, x, clip, g, m, pad, on, off, active=1, L=L, H=H):
     """Rows and voiced samples of one stream from the clip path's kernels."""
     from vad_amd import scores as SC, segments as SG
     lab = SC.score_labels(cuda(x), on, off) if on is not None else cuda(x)
@@ -197,7 +208,7 @@ def ffn(name, arith="split_f16"):
 
 
 @functools.lru_cache(maxsize=None)
-def audio(S, T, seed=1200):
+def audio(S, T, seed=1200, L=L, H=H):
     keep = L - H
     clips = np.stack([O.synth_clip(H * T + keep, seed=seed + s)[:H * T + keep] for s in range(S)])
     carry = np.ascontiguousarray(clips[:, :keep])
@@ -212,11 +223,12 @@ def batch(torch, S, clf, carry, **kw):
     return sb
 
 
-def run_pair(torch, clf, S, K, T, dtype, graph, active, record_seq=False, **kw):
+def run_pair(torch, clf, S, K, T, dtype, graph, active, record_seq=False, L=L, H=H, **kw):
     """A scored and an unscored batch on the same hops: labels (T, S), scores
     (T, S), and the state equalities checked after every block."""
     dt = getattr(torch, dtype)
-    carry, hops = audio(S, T)
+    carry, hops = audio(S, T, L=L, H=H)
+    kw["cfg"] = framing(L, H)
     dh = cuda(hops).to(dt)
     a = batch(torch, S, clf, carry, hops_per_step=K, input_dtype=dt, scores=True, active=active, **kw)
     b = batch(torch, S, clf, carry, hops_per_step=K, input_dtype=dt, **kw)
@@ -275,15 +287,17 @@ def test_ffn_hop_scores_accuracy(torch_cuda, net):
     path's exact-f32 scores on the same rows against the same value.  Bound:
     twice the yardstick (another fp32 summation order) plus 8 * 2^-24 (the
     shared softmax function's own bound in test_ffn_scores)."""
-    torch = torch_cuda
+    ffn_scores_accuracy(torch_cuda, net, 9, 40, "float32")
+
+
+def ffn_scores_accuracy(torch, net, S, T, dtype, L=L, H=H):
     from vad_amd import scores as SC
     from vad_amd.plan import window_logits
     clf, exact = ffn(net), ffn(net, "f32")
     n_cls = clf.layers[-1][1].shape[0]
-    S, T = 9, 40
     worst_hop = worst_clip = 0.0
     for active in range(n_cls):
-        lab, sc, seq, _ = run_pair(torch, clf, S, 1, T, "float32", False, active, record_seq=True)
+        lab, sc, seq, sb = run_pair(torch, clf, S, 1, T, dtype, False, active, record_seq=True, L=L, H=H)
         for s in range(S):
             x = O.analyser_features(seq[s].cpu().numpy().astype(np.float64))[:, :clf.layers[0][0].shape[0]]
             _, p = O.ffn_forward(x, clf.layers)
@@ -297,6 +311,7 @@ def test_ffn_hop_scores_accuracy(torch_cuda, net):
     print(f"\n{net}: max |hop score - f64| = {worst_hop:.3e} = {worst_hop * 2 ** 24:.2f} * 2^-24; "
           f"clip exact-f32 yardstick {worst_clip:.3e} = {worst_clip * 2 ** 24:.2f} * 2^-24")
     assert worst_hop <= 2 * worst_clip + 8 * 2.0 ** -24, (net, worst_hop, worst_clip)
+    return sb
 
 
 def test_scored_hop_entries_refuse(torch_cuda):
@@ -358,10 +373,11 @@ def tree_with_scores():
     return with_counts(R.fixture_tree())
 
 
-def check_tree_scores(torch, clf, S, K, T, dtype, graph, walk):
+def check_tree_scores(torch, clf, S, K, T, dtype, graph, walk, L=L, H=H):
     from vad_amd import scores as SC
     for active in (0, 1):
-        lab, sc, seq, sb = run_pair(torch, clf, S, K, T, dtype, graph, active, record_seq=(K == 1), tree_walk=walk)
+        lab, sc, seq, sb = run_pair(torch, clf, S, K, T, dtype, graph, active, record_seq=(K == 1), tree_walk=walk,
+                                    L=L, H=H)
         table = clf.score_table(active)
         assert ((sc[5:] > 0.5) == (lab[5:] == active)).all()
         assert np.isin(sc[5:], table).all()
@@ -369,6 +385,7 @@ def check_tree_scores(torch, clf, S, K, T, dtype, graph, walk):
             for s in range(S):
                 want = SC.tree_window_scores(clf, seq[s], active=active).cpu().numpy()
                 assert np.array_equal(sc[5:, s].view(np.uint32), want.view(np.uint32)), (walk, active, s)
+    check_tree_scores.last = sb
     return sc
 
 
@@ -382,6 +399,29 @@ def test_tree_hop_scores(torch_cuda, S, K, dtype, graph, walk):
     if K > 1:  # blocks give the one-hop steps' scores
         one = check_tree_scores(torch, tree_with_scores(), S, 1, T, dtype, False, walk)
         assert np.array_equal(sc.view(np.uint32), one.view(np.uint32))
+
+
+# ---------------------------------------------------------------------------
+# the 16-chunk builds of the scored kernels
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["float32", "int16"])
+@pytest.mark.parametrize("which", ["ffn", "tree"])
+@pytest.mark.parametrize("L16,H16", [(512, 160), (1000, 333)])
+def test_hop_scores_16_chunk_builds(torch_cuda, L16, H16, which, dtype):
+    """Frames past 448 samples (the transform reads the first 512): the
+    per-hop comparisons above -- the FFN's scores against the float64 forward
+    under test_ffn_hop_scores_accuracy's bound, the tree's against the clip
+    kernel's bit for bit, both walks -- in the 16-chunk builds."""
+    torch = torch_cuda
+    if which == "ffn":
+        sb = ffn_scores_accuracy(torch, "bl13", 5, 24, dtype, L=L16, H=H16)
+        assert is_16_chunk(sb) and sb._hop_name == "vad_stream_hops_scores" + ("_i16" if dtype == "int16" else "")
+    else:
+        for walk in ("auto", "global"):
+            check_tree_scores(torch, tree_with_scores(), 5, 1, 24, dtype, False, walk, L=L16, H=H16)
+            sb = check_tree_scores.last
+            assert is_16_chunk(sb) and sb.tree_walk == walk
+            assert sb._hop_name == "vad_stream_hops_tree_scores" + ("_i16" if dtype == "int16" else "")
 
 
 def test_tree_hop_scores_table_past_lds(torch_cuda):

@@ -120,6 +120,9 @@ SIGNATURES = {
     "vad_stream_step_tree": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp,
                                      c_vp]),
     "vad_stream_tree_max_lds_nodes": (c_i64, [c_vp]),
+    "vad_stream_hop_table_bytes": (c_i64, [c_vp, c_vp]),
+    "vad_stream_hop_tree_table_bytes": (c_i64, [c_vp, c_vp, c_i32]),
+    "vad_stream_hop_block_waves": (c_i32, [c_i64, c_i64, c_i32]),
     "vad_tree_plan_set_scores": (c_int, [c_vp, c_vp, c_i32]),
     "vad_tree_plan_score_classes": (c_i32, [c_vp]),
     **{"vad_stream_hops_scores" + t: (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32, c_i64,

@@ -1293,6 +1293,28 @@ int64_t vad_stream_tree_max_lds_nodes(const vad_mfcc_plan* plan) {
   return stream_tree_max_lds_nodes(plan->hop_blob_n);
 }
 
+// The hop kernels' launch rule as a query: the launchers call the same
+// functions (stream_hop_block_waves and the table sizes).
+int64_t vad_stream_hop_table_bytes(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn) {
+  if (!plan || !ffn || !plan->hop_blob || plan->hop_blob_n <= 0) return VAD_EINVAL;
+  return (int64_t)stream_hop_ffn_table_bytes(plan->hop_blob_n, ffn->net);
+}
+
+int64_t vad_stream_hop_tree_table_bytes(const vad_mfcc_plan* plan, const vad_tree_plan* tree, int32_t walk) {
+  if (!plan || !tree || !plan->hop_blob || plan->hop_blob_n <= 0) return VAD_EINVAL;
+  if (walk != VAD_TREE_WALK_AUTO && walk != VAD_TREE_WALK_GLOBAL) return VAD_EINVAL;
+  return (int64_t)stream_hop_tree_table_bytes(
+      plan->hop_blob_n,
+      stream_tree_lds_nodes(plan->hop_blob_n, tree->cnodes_dev, tree->n_nodes, walk == VAD_TREE_WALK_GLOBAL));
+}
+
+int32_t vad_stream_hop_block_waves(int64_t table_bytes, int64_t n_streams, int32_t n_hops) {
+  if (table_bytes < 0 || n_streams < 0 || n_hops < 0) return VAD_EINVAL;
+  if (n_streams == 0 || n_hops == 0) return 0;  // the entries return before any launch
+  const int waves = stream_hop_block_waves((size_t)table_bytes, n_streams, n_hops);
+  return waves > 0 ? waves : VAD_EINVAL;  // the launchers refuse tables that leave no wave its scratch
+}
+
 static int stream_hops_tree_entry(const vad_mfcc_plan* plan, const vad_tree_plan* tree, float* frames,
                                   int64_t frame_stride, int32_t frame_len, const void* hop, int hop_bytes,
                                   int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,

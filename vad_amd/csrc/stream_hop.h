@@ -60,23 +60,16 @@ constexpr int kHopMinWaves = 4;
 // stream per block spreads over more CUs (K = 8: 8.2 vs 8.4 us per hop,
 // K = 32: 7.4 vs 7.6 with 4 per block)
 constexpr int kHopMinWavesK = 1;
+// The rule is stream_hop_block_waves (stream_kernel.hip), which the C ABI
+// also exports as a query: vad_stream_hop_block_waves.
 
 template <auto K7, auto K16, class... Args>
 hipError_t launch_hop_kernels(size_t tables, int len, int64_t n_streams, int n_hops, hipStream_t st,
                               const Args&... args) {
   if (n_streams <= 0 || n_hops <= 0) return hipSuccess;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-      n_cu = 256;
-  }
-  int waves = n_hops > 1 ? kHopMinWavesK : kHopMinWaves;
-  while (waves < 16 && (int64_t)waves * n_cu < n_streams) waves <<= 1;
-  while (waves > 1 && tables + (size_t)waves * kHopWaveFloats * sizeof(float) > kHopLdsBytes) waves >>= 1;
+  const int waves = stream_hop_block_waves(tables, n_streams, n_hops);
+  if (waves <= 0) return hipErrorInvalidValue;
   const size_t smem = tables + (size_t)waves * kHopWaveFloats * sizeof(float);
-  if (smem > kHopLdsBytes) return hipErrorInvalidValue;
   static std::atomic<unsigned long long> attr_done{0};  // per kernel function: this template's own
   static std::atomic<unsigned long long> attr_done16{0};
   const bool small = len <= 7 * 64;

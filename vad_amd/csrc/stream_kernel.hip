@@ -248,6 +248,29 @@ __global__ __launch_bounds__(1024) void stream_hop_sessions_denoise_kernel(
 #undef VAD_HOP_SCORE
 }
 
+// The launch rule of every hop kernel (stream_hop.h has its reasons and
+// measurements): waves per block, 0 when not even one wave's scratch fits.
+int stream_hop_block_waves(size_t tables, int64_t n_streams, int n_hops) {
+  if (tables + kHopWaveFloats * sizeof(float) > kHopLdsBytes) return 0;  // before any device call
+  static std::atomic<int> n_cu_seen{0};
+  int n_cu = n_cu_seen.load(std::memory_order_relaxed);
+  if (n_cu == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
+      n_cu = 256;
+    n_cu_seen.store(n_cu, std::memory_order_relaxed);
+  }
+  int waves = n_hops > 1 ? kHopMinWavesK : kHopMinWaves;
+  while (waves < 16 && (int64_t)waves * n_cu < n_streams) waves <<= 1;
+  while (waves > 1 && tables + (size_t)waves * kHopWaveFloats * sizeof(float) > kHopLdsBytes) waves >>= 1;
+  return waves;
+}
+
+size_t stream_hop_ffn_table_bytes(int blob_n, const FfnDev& net) {
+  return (size_t)(blob_n + net.wraw_n) * sizeof(float);
+}
+
 template <class TH>
 static hipError_t launch_stream_hop_sessions_t(const float* blob, int blob_n, int nf, int n_taps, const FfnDev& net,
                                                float* frames, int64_t fstride, int len, const void* hop,
@@ -256,7 +279,7 @@ static hipError_t launch_stream_hop_sessions_t(const float* blob, int blob_n, in
                                                int64_t lab_kstride, int active, float* scores, int64_t score_kstride,
                                                const HopDenoise* dn, const int* hop_counts, uint8_t* restart,
                                                hipStream_t st) {
-  const size_t tables = (size_t)(blob_n + net.wraw_n) * sizeof(float);
+  const size_t tables = stream_hop_ffn_table_bytes(blob_n, net);
   if (dn)
     return launch_hop_kernels<&stream_hop_sessions_denoise_kernel<7, TH>, &stream_hop_sessions_denoise_kernel<16, TH>>(
         tables, len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, net, frames, fstride, len, (const TH*)hop, hstride,
@@ -275,7 +298,7 @@ static hipError_t launch_stream_hop_t(const float* blob, int blob_n, int nf, int
                                       uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
                                       hipStream_t st) {
   return launch_hop_kernels<&stream_hop_kernel<7, TH>, &stream_hop_kernel<16, TH>>(
-      (size_t)(blob_n + net.wraw_n) * sizeof(float), len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, net,
+      stream_hop_ffn_table_bytes(blob_n, net), len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, net,
       frames, fstride, len, (const TH*)hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops,
       hop_kstride, lab_kstride);
 }
@@ -288,7 +311,7 @@ static hipError_t launch_stream_hop_scores_t(const float* blob, int blob_n, int 
                                              int64_t lab_kstride, int active, float* scores, int64_t score_kstride,
                                              hipStream_t st) {
   return launch_hop_kernels<&stream_hop_scores_kernel<7, TH>, &stream_hop_scores_kernel<16, TH>>(
-      (size_t)(blob_n + net.wraw_n) * sizeof(float), len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, net,
+      stream_hop_ffn_table_bytes(blob_n, net), len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, net,
       frames, fstride, len, (const TH*)hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops,
       hop_kstride, lab_kstride, active, scores, score_kstride);
 }
@@ -301,7 +324,7 @@ static hipError_t launch_stream_hop_denoise_t(const float* blob, int blob_n, int
                                               int64_t lab_kstride, int active, float* scores, int64_t score_kstride,
                                               const HopDenoise& dn, hipStream_t st) {
   return launch_hop_kernels<&stream_hop_denoise_kernel<7, TH>, &stream_hop_denoise_kernel<16, TH>>(
-      (size_t)(blob_n + net.wraw_n) * sizeof(float), len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, net,
+      stream_hop_ffn_table_bytes(blob_n, net), len, n_streams, n_hops, st, blob, blob_n, nf, n_taps, net,
       frames, fstride, len, (const TH*)hop, hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops,
       hop_kstride, lab_kstride, active, scores, score_kstride, dn);
 }

@@ -132,6 +132,15 @@ int64_t stream_tree_max_lds_nodes(int blob_n) {
   return room > 0 ? room / (int64_t)sizeof(TreeNodeC) : 0;
 }
 
+// The nodes a launch stages: the whole table, or none (the global walk).
+int stream_tree_lds_nodes(int blob_n, const TreeNodeC* cnodes, int n_nodes, bool force_global) {
+  return !force_global && cnodes && n_nodes <= stream_tree_max_lds_nodes(blob_n) ? n_nodes : 0;
+}
+
+size_t stream_hop_tree_table_bytes(int blob_n, int lds_nodes) {
+  return (size_t)blob_n * sizeof(float) + (size_t)lds_nodes * sizeof(TreeNodeC);
+}
+
 template <class TH>
 static hipError_t launch_stream_hop_tree_t(const float* blob, int blob_n, int nf, int n_taps, const TreeNodeC* cnodes,
                                            const TreeNode* nodes, int n_nodes, int lds_nodes, float* frames,
@@ -139,7 +148,7 @@ static hipError_t launch_stream_hop_tree_t(const float* blob, int blob_n, int nf
                                            int64_t n_streams, int mfcc_n, float* ring, int* count, uint8_t* labels,
                                            int n_hops, int64_t hop_kstride, int64_t lab_kstride, hipStream_t st) {
   return launch_hop_kernels<&stream_hop_tree_kernel<7, TH>, &stream_hop_tree_kernel<16, TH>>(
-      (size_t)blob_n * sizeof(float) + (size_t)lds_nodes * sizeof(TreeNodeC), len, n_streams, n_hops, st, blob, blob_n,
+      stream_hop_tree_table_bytes(blob_n, lds_nodes), len, n_streams, n_hops, st, blob, blob_n,
       nf, n_taps, cnodes, nodes, n_nodes, lds_nodes, frames, fstride, len, (const TH*)hop, hstride, hlen, n_streams,
       mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride);
 }
@@ -153,7 +162,7 @@ static hipError_t launch_stream_hop_tree_scores_t(const float* blob, int blob_n,
                                                   int64_t hop_kstride, int64_t lab_kstride, const float* node_score,
                                                   float* scores, int64_t score_kstride, hipStream_t st) {
   return launch_hop_kernels<&stream_hop_tree_scores_kernel<7, TH>, &stream_hop_tree_scores_kernel<16, TH>>(
-      (size_t)blob_n * sizeof(float) + (size_t)lds_nodes * sizeof(TreeNodeC), len, n_streams, n_hops, st, blob, blob_n,
+      stream_hop_tree_table_bytes(blob_n, lds_nodes), len, n_streams, n_hops, st, blob, blob_n,
       nf, n_taps, cnodes, nodes, n_nodes, lds_nodes, frames, fstride, len, (const TH*)hop, hstride, hlen, n_streams,
       mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, node_score, scores, score_kstride);
 }
@@ -165,9 +174,9 @@ hipError_t launch_stream_hop_tree(const float* blob, int blob_n, int nf, int n_t
                                   int64_t fstride, int len, const void* hop, int hop_bytes, int64_t hstride, int hlen,
                                   int64_t n_streams, int mfcc_n, float* ring, int* count, uint8_t* labels, int n_hops,
                                   int64_t hop_kstride, int64_t lab_kstride, hipStream_t st) {
-  const bool lds = !force_global && cnodes && n_nodes <= stream_tree_max_lds_nodes(blob_n);
+  const int lds_nodes = stream_tree_lds_nodes(blob_n, cnodes, n_nodes, force_global);
   const auto launch = hop_bytes == 2 ? launch_stream_hop_tree_t<int16_t> : launch_stream_hop_tree_t<float>;
-  return launch(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds ? n_nodes : 0, frames, fstride, len, hop,
+  return launch(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds_nodes, frames, fstride, len, hop,
                 hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, st);
 }
 
@@ -180,9 +189,9 @@ hipError_t launch_stream_hop_tree_scores(const float* blob, int blob_n, int nf, 
                                          uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
                                          const float* node_score, float* scores, int64_t score_kstride,
                                          hipStream_t st) {
-  const bool lds = !force_global && cnodes && n_nodes <= stream_tree_max_lds_nodes(blob_n);
+  const int lds_nodes = stream_tree_lds_nodes(blob_n, cnodes, n_nodes, force_global);
   const auto launch = hop_bytes == 2 ? launch_stream_hop_tree_scores_t<int16_t> : launch_stream_hop_tree_scores_t<float>;
-  return launch(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds ? n_nodes : 0, frames, fstride, len, hop,
+  return launch(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds_nodes, frames, fstride, len, hop,
                 hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, node_score,
                 scores, score_kstride, st);
 }
@@ -197,7 +206,7 @@ static hipError_t launch_stream_hop_tree_denoise_t(const float* blob, int blob_n
                                                    float* scores, int64_t score_kstride, const HopDenoise& dn,
                                                    hipStream_t st) {
   return launch_hop_kernels<&stream_hop_tree_denoise_kernel<7, TH>, &stream_hop_tree_denoise_kernel<16, TH>>(
-      (size_t)blob_n * sizeof(float) + (size_t)lds_nodes * sizeof(TreeNodeC), len, n_streams, n_hops, st, blob, blob_n,
+      stream_hop_tree_table_bytes(blob_n, lds_nodes), len, n_streams, n_hops, st, blob, blob_n,
       nf, n_taps, cnodes, nodes, n_nodes, lds_nodes, frames, fstride, len, (const TH*)hop, hstride, hlen, n_streams,
       mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, node_score, scores, score_kstride, dn);
 }
@@ -210,10 +219,10 @@ hipError_t launch_stream_hop_tree_denoise(const float* blob, int blob_n, int nf,
                                           uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
                                           const float* node_score, float* scores, int64_t score_kstride,
                                           const HopDenoise& dn, hipStream_t st) {
-  const bool lds = !force_global && cnodes && n_nodes <= stream_tree_max_lds_nodes(blob_n);
+  const int lds_nodes = stream_tree_lds_nodes(blob_n, cnodes, n_nodes, force_global);
   const auto launch =
       hop_bytes == 2 ? launch_stream_hop_tree_denoise_t<int16_t> : launch_stream_hop_tree_denoise_t<float>;
-  return launch(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds ? n_nodes : 0, frames, fstride, len, hop,
+  return launch(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds_nodes, frames, fstride, len, hop,
                 hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, node_score,
                 scores, score_kstride, dn, st);
 }
@@ -227,7 +236,7 @@ static hipError_t launch_stream_hop_tree_sessions_t(const float* blob, int blob_
                                                     int64_t hop_kstride, int64_t lab_kstride, const float* node_score,
                                                     float* scores, int64_t score_kstride, const HopDenoise* dn,
                                                     const int* hop_counts, uint8_t* restart, hipStream_t st) {
-  const size_t tables = (size_t)blob_n * sizeof(float) + (size_t)lds_nodes * sizeof(TreeNodeC);
+  const size_t tables = stream_hop_tree_table_bytes(blob_n, lds_nodes);
   if (dn)
     return launch_hop_kernels<&stream_hop_tree_sessions_denoise_kernel<7, TH>,
                               &stream_hop_tree_sessions_denoise_kernel<16, TH>>(
@@ -249,10 +258,10 @@ hipError_t launch_stream_hop_tree_sessions(const float* blob, int blob_n, int nf
                                            const float* node_score, float* scores, int64_t score_kstride,
                                            const HopDenoise* dn, const int* hop_counts, uint8_t* restart,
                                            hipStream_t st) {
-  const bool lds = !force_global && cnodes && n_nodes <= stream_tree_max_lds_nodes(blob_n);
+  const int lds_nodes = stream_tree_lds_nodes(blob_n, cnodes, n_nodes, force_global);
   const auto launch =
       hop_bytes == 2 ? launch_stream_hop_tree_sessions_t<int16_t> : launch_stream_hop_tree_sessions_t<float>;
-  return launch(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds ? n_nodes : 0, frames, fstride, len, hop,
+  return launch(blob, blob_n, nf, n_taps, cnodes, nodes, n_nodes, lds_nodes, frames, fstride, len, hop,
                 hstride, hlen, n_streams, mfcc_n, ring, count, labels, n_hops, hop_kstride, lab_kstride, node_score,
                 scores, score_kstride, dn, hop_counts, restart, st);
 }

@@ -163,6 +163,15 @@ hipError_t launch_stream_push(float* frames, int64_t fstride, int len, const voi
 // hop kernel walks from LDS beside a blob of blob_n floats; force_global walks
 // a smaller one from global memory too.
 int64_t stream_tree_max_lds_nodes(int blob_n);
+// The hop kernels' launch rule (stream_kernel.hip; launch_hop_kernels in
+// stream_hop.h calls it): waves per block of a launch whose blocks stage
+// `tables` bytes, on the current device; 0 when the tables leave no room for
+// one wave's scratch.  The staged bytes of an FFN launch and of a tree launch
+// (stream_tree_lds_nodes: the nodes it stages, 0 for a global walk).
+int stream_hop_block_waves(size_t tables, int64_t n_streams, int n_hops);
+size_t stream_hop_ffn_table_bytes(int blob_n, const FfnDev& net);
+int stream_tree_lds_nodes(int blob_n, const TreeNodeC* cnodes, int n_nodes, bool force_global);
+size_t stream_hop_tree_table_bytes(int blob_n, int lds_nodes);
 hipError_t launch_stream_hop_tree(const float* blob, int blob_n, int nf, int n_taps, const TreeNodeC* cnodes,
                                   const TreeNode* nodes, int n_nodes, bool force_global, float* frames,
                                   int64_t fstride, int len, const void* hop, int hop_bytes, int64_t hstride, int hlen,

@@ -276,6 +276,26 @@ class StreamBatch:
         self._need_denoise()
         return self._est * self._UNITS
 
+    @property
+    def block_waves(self):
+        """Waves (streams) per block of this batch's hop launches on the
+        current device: vad_stream_hop_block_waves, the rule the launcher
+        itself applies.  kernel="hop" only."""
+        if self.kernel != "hop":
+            raise ValueError("block_waves is the one-kernel hop's launch shape: kernel='three' has none")
+        lib = _lib.lib()
+        if self.is_tree:
+            nbytes = lib.vad_stream_hop_tree_table_bytes(self.plan.handle, self.ffn.plan.handle,
+                                                         _TREE_WALKS[self.tree_walk])
+        else:
+            nbytes = lib.vad_stream_hop_table_bytes(self.plan.handle, self.ffn.plan.handle)
+        if nbytes < 0:
+            _lib.check(int(nbytes), "vad_stream_hop_table_bytes")
+        waves = lib.vad_stream_hop_block_waves(nbytes, self.n, self.K)
+        if waves < 0:
+            _lib.check(int(waves), "vad_stream_hop_block_waves")
+        return int(waves)
+
     def load_noise(self, frames):
         """frames (S, n, frame_size), n = 1..5, a CUDA tensor of the batch's
         input dtype: their power rows become the noise rows, in order, and
