@@ -514,8 +514,38 @@ int vad_simple_features(const float* frames, int64_t n_frames, int32_t frame_len
  * stream from the rows feats (S, noise_buf_len, 7) of its init frames: noise
  * buffer, the three thresholds as plain means, status 0, silence 1,
  * noise_pointer 0, frame_number 0.
+ *
+ * Sessions (vad_simple_stream_block_sessions_f32 / _i16,
+ * vad_simple_stream_state_sessions): the sibling entry's arguments, then three
+ * per-stream device arrays read inside the kernels, so callers join, leave
+ * and stall without a host step:
+ *   frame_counts (S) int32: stream s takes n_s = min(max(frame_counts[s], 0),
+ *     n_frames) frames, rows 0..n_s-1 of its column of the block.
+ *   restart (S) uint8: nonzero makes the stream fresh before its frames of
+ *     this call (its state record all zero, init_left = noise_buf_len); the
+ *     kernel stores 0 back, so a flag set once restarts once, also when a
+ *     captured graph is replayed.
+ *   init_left (S) int32, read and written: the frames the stream still needs
+ *     before it is initialised (0: initialised; set it to 0 after
+ *     vad_simple_stream_init, to noise_buf_len with a zeroed record for a new
+ *     batch).  While it is positive each frame taken is an init frame: its
+ *     feature row fills noise row noise_buf_len - init_left, and the last one
+ *     does what vad_simple_stream_init does on those noise_buf_len rows.
+ *     Frames after it in the same block are classified.  The state record
+ *     above does not change.
+ *   labels: VAD_LABEL_INIT in the row of an init frame (never copied to
+ *     voiced), VAD_LABEL_NO_HOP in rows n_s..n_frames-1; features_out rows
+ *     n_s..n_frames-1 are not written by the one-kernel form (the two-launch
+ *     form computes all rows).  voiced_len[s] counts the frames labelled 1.
+ *   A stream with n_s = 0 and no restart keeps every byte of its record and
+ *   its init_left.  With every count n_frames, no restart and every init_left
+ *   0, all outputs equal the sibling entry's bit for bit.
+ * VAD_EINVAL as for the sibling, and for a null frame_counts, restart or
+ * init_left or a frame_counts / init_left that is not 4-byte aligned.
+ * n_frames == 0: VAD_OK, nothing written, no flag consumed.
  * ------------------------------------------------------------------------- */
 #define VAD_SIMPLE_MAX_NOISE 64
+#define VAD_LABEL_INIT 253 /* a label row that holds one of the stream's init frames (sessions) */
 size_t vad_simple_stream_state_bytes(int32_t noise_buf_len); /* 0 outside 1..VAD_SIMPLE_MAX_NOISE */
 int vad_simple_stream_init(const double* feats, int64_t n_streams, int32_t noise_buf_len, void* state, void* stream);
 int vad_simple_stream_block_f32(const float* frames, int64_t block_stride, int64_t stream_stride, int32_t frame_len,
@@ -530,6 +560,24 @@ int vad_simple_stream_block_i16(const int16_t* frames, int64_t block_stride, int
                                 void* stream);
 int vad_simple_stream_state(const double* feats, int64_t n_streams, int32_t n_frames, int32_t noise_buf_len,
                             void* state, uint8_t* labels, int64_t label_block_stride, void* stream);
+int vad_simple_stream_block_sessions_f32(const float* frames, int64_t block_stride, int64_t stream_stride,
+                                         int32_t frame_len, int32_t fft_len, int32_t pad, int32_t band_bins,
+                                         int64_t n_streams, int32_t n_frames, int32_t noise_buf_len, void* state,
+                                         uint8_t* labels, int64_t label_block_stride, double* features_out,
+                                         float* voiced, int64_t voiced_stride, int32_t* voiced_len,
+                                         const int32_t* frame_counts, uint8_t* restart, int32_t* init_left,
+                                         void* stream);
+int vad_simple_stream_block_sessions_i16(const int16_t* frames, int64_t block_stride, int64_t stream_stride,
+                                         int32_t frame_len, int32_t fft_len, int32_t pad, int32_t band_bins,
+                                         int64_t n_streams, int32_t n_frames, int32_t noise_buf_len, void* state,
+                                         uint8_t* labels, int64_t label_block_stride, double* features_out,
+                                         int16_t* voiced, int64_t voiced_stride, int32_t* voiced_len,
+                                         const int32_t* frame_counts, uint8_t* restart, int32_t* init_left,
+                                         void* stream);
+int vad_simple_stream_state_sessions(const double* feats, int64_t n_streams, int32_t n_frames, int32_t noise_buf_len,
+                                     void* state, uint8_t* labels, int64_t label_block_stride,
+                                     const int32_t* frame_counts, uint8_t* restart, int32_t* init_left,
+                                     void* stream);
 
 /* ---------------------------------------------------------------------------
  * Streaming: S independent analyser streams advanced by one frame each

@@ -27,6 +27,7 @@ FFN_SPLIT_F16 = 1
 TREE_WALK_AUTO = 0
 TREE_WALK_GLOBAL = 1
 LABEL_NO_HOP = 254
+LABEL_INIT = 253
 CSV_TILE = 4096
 CSV_CARRY_PASS = 256
 CSV_MAX_LINE = 4096
@@ -87,6 +88,13 @@ SIGNATURES = {
     "vad_simple_stream_block_i16": (c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_i32, c_vp,
                                             c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "vad_simple_stream_state": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    # sessions: the sibling's arguments, then frame_counts, restart, init_left, stream
+    **{"vad_simple_stream_block_sessions_" + t: (c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32,
+                                                         c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                                         c_vp, c_vp])
+       for t in ("f32", "i16")},
+    "vad_simple_stream_state_sessions": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                                 c_vp]),
     "vad_scale_workspace_bytes": (c_sz, []),
     "vad_scale_features": (c_int, [c_vp, c_i64, c_i32, c_vp, c_sz, c_vp]),
     "vad_format_csv_rows": (c_i64, [c_vp, c_i64, c_i32, ctypes.c_double, c_vp, c_i64]),

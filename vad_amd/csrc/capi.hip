@@ -818,23 +818,50 @@ int vad_simple_stream_init(const double* feats, int64_t n_streams, int32_t noise
   return (int)launch_simple_stream_init(feats, n_streams, noise_buf_len, state, (hipStream_t)stream);
 }
 
-int vad_simple_stream_state(const double* feats, int64_t n_streams, int32_t n_frames, int32_t noise_buf_len,
-                            void* state, uint8_t* labels, int64_t label_block_stride, void* stream) {
+// The session words of the sessions entries: all three, the int32 ones aligned.
+static bool simple_sessions_ok(const int32_t* frame_counts, const uint8_t* restart, const int32_t* init_left) {
+  return frame_counts && restart && init_left && reinterpret_cast<uintptr_t>(frame_counts) % 4 == 0 &&
+         reinterpret_cast<uintptr_t>(init_left) % 4 == 0;
+}
+
+static int simple_stream_state_entry(const double* feats, int64_t n_streams, int32_t n_frames, int32_t noise_buf_len,
+                                     void* state, uint8_t* labels, int64_t label_block_stride, bool sessions,
+                                     const int32_t* frame_counts, uint8_t* restart, int32_t* init_left,
+                                     void* stream) {
   if (!simple_stream_common_ok(n_streams, noise_buf_len, state) || n_frames < 0 || !feats || !labels)
     return VAD_EINVAL;
   if (n_frames > 1 && label_block_stride < n_streams) return VAD_EINVAL;
+  if (sessions && !simple_sessions_ok(frame_counts, restart, init_left)) return VAD_EINVAL;
   if (n_frames == 0) return VAD_OK;
   return (int)launch_simple_stream_state(feats, n_streams, n_frames, noise_buf_len, state, labels, label_block_stride,
-                                         nullptr, 0, 0, 0, nullptr, 0, nullptr, (hipStream_t)stream);
+                                         nullptr, 0, 0, 0, nullptr, 0, nullptr, frame_counts, restart, init_left,
+                                         (hipStream_t)stream);
+}
+
+int vad_simple_stream_state(const double* feats, int64_t n_streams, int32_t n_frames, int32_t noise_buf_len,
+                            void* state, uint8_t* labels, int64_t label_block_stride, void* stream) {
+  return simple_stream_state_entry(feats, n_streams, n_frames, noise_buf_len, state, labels, label_block_stride,
+                                   false, nullptr, nullptr, nullptr, stream);
+}
+
+int vad_simple_stream_state_sessions(const double* feats, int64_t n_streams, int32_t n_frames, int32_t noise_buf_len,
+                                     void* state, uint8_t* labels, int64_t label_block_stride,
+                                     const int32_t* frame_counts, uint8_t* restart, int32_t* init_left,
+                                     void* stream) {
+  return simple_stream_state_entry(feats, n_streams, n_frames, noise_buf_len, state, labels, label_block_stride, true,
+                                   frame_counts, restart, init_left, stream);
 }
 
 static int simple_stream_block_entry(const void* frames, int in_bytes, int64_t block_stride, int64_t stream_stride,
                                      int32_t frame_len, int32_t fft_len, int32_t pad, int32_t band_bins,
                                      int64_t n_streams, int32_t n_frames, int32_t noise_buf_len, void* state,
                                      uint8_t* labels, int64_t label_block_stride, double* features_out, void* voiced,
-                                     int64_t voiced_stride, int32_t* voiced_len, void* stream) {
+                                     int64_t voiced_stride, int32_t* voiced_len, bool sessions,
+                                     const int32_t* frame_counts, uint8_t* restart, int32_t* init_left,
+                                     void* stream) {
   if (!simple_stream_common_ok(n_streams, noise_buf_len, state) || n_frames < 0 || !frames || !labels)
     return VAD_EINVAL;
+  if (sessions && !simple_sessions_ok(frame_counts, restart, init_left)) return VAD_EINVAL;
   if (frame_len < 2 || frame_len > 8192 || pad < 0 || fft_len != frame_len + 2 * pad || fft_len > 8193)
     return VAD_EINVAL;
   if (band_bins < 1 || 4 * (int64_t)band_bins > fft_len) return VAD_EINVAL;  // "FFTN is small"
@@ -853,7 +880,8 @@ static int simple_stream_block_entry(const void* frames, int in_bytes, int64_t b
   if (one_kernel)
     return (int)launch_simple_stream_block(frames, in_bytes, block_stride, stream_stride, frame_len, fft_len, pad,
                                            band_bins, n_streams, n_frames, noise_buf_len, state, labels,
-                                           label_block_stride, features_out, voiced, voiced_stride, voiced_len, st);
+                                           label_block_stride, features_out, voiced, voiced_stride, voiced_len,
+                                           frame_counts, restart, init_left, st);
   // any other length: the rows of every (frame, stream) pair, then the state steps
   const float* x = static_cast<const float*>(frames);
   if (n_frames == 1 || block_stride == n_streams * stream_stride) {
@@ -866,7 +894,8 @@ static int simple_stream_block_entry(const void* frames, int in_bytes, int64_t b
   }
   return (int)launch_simple_stream_state(features_out, n_streams, n_frames, noise_buf_len, state, labels,
                                          label_block_stride, x, block_stride, stream_stride, frame_len,
-                                         static_cast<float*>(voiced), voiced_stride, voiced_len, st);
+                                         static_cast<float*>(voiced), voiced_stride, voiced_len, frame_counts, restart,
+                                         init_left, st);
 }
 
 int vad_simple_stream_block_f32(const float* frames, int64_t block_stride, int64_t stream_stride, int32_t frame_len,
@@ -876,7 +905,8 @@ int vad_simple_stream_block_f32(const float* frames, int64_t block_stride, int64
                                 void* stream) {
   return simple_stream_block_entry(frames, 4, block_stride, stream_stride, frame_len, fft_len, pad, band_bins,
                                    n_streams, n_frames, noise_buf_len, state, labels, label_block_stride,
-                                   features_out, voiced, voiced_stride, voiced_len, stream);
+                                   features_out, voiced, voiced_stride, voiced_len, false, nullptr, nullptr, nullptr,
+                                   stream);
 }
 
 int vad_simple_stream_block_i16(const int16_t* frames, int64_t block_stride, int64_t stream_stride, int32_t frame_len,
@@ -886,7 +916,34 @@ int vad_simple_stream_block_i16(const int16_t* frames, int64_t block_stride, int
                                 void* stream) {
   return simple_stream_block_entry(frames, 2, block_stride, stream_stride, frame_len, fft_len, pad, band_bins,
                                    n_streams, n_frames, noise_buf_len, state, labels, label_block_stride,
-                                   features_out, voiced, voiced_stride, voiced_len, stream);
+                                   features_out, voiced, voiced_stride, voiced_len, false, nullptr, nullptr, nullptr,
+                                   stream);
+}
+
+int vad_simple_stream_block_sessions_f32(const float* frames, int64_t block_stride, int64_t stream_stride,
+                                         int32_t frame_len, int32_t fft_len, int32_t pad, int32_t band_bins,
+                                         int64_t n_streams, int32_t n_frames, int32_t noise_buf_len, void* state,
+                                         uint8_t* labels, int64_t label_block_stride, double* features_out,
+                                         float* voiced, int64_t voiced_stride, int32_t* voiced_len,
+                                         const int32_t* frame_counts, uint8_t* restart, int32_t* init_left,
+                                         void* stream) {
+  return simple_stream_block_entry(frames, 4, block_stride, stream_stride, frame_len, fft_len, pad, band_bins,
+                                   n_streams, n_frames, noise_buf_len, state, labels, label_block_stride,
+                                   features_out, voiced, voiced_stride, voiced_len, true, frame_counts, restart,
+                                   init_left, stream);
+}
+
+int vad_simple_stream_block_sessions_i16(const int16_t* frames, int64_t block_stride, int64_t stream_stride,
+                                         int32_t frame_len, int32_t fft_len, int32_t pad, int32_t band_bins,
+                                         int64_t n_streams, int32_t n_frames, int32_t noise_buf_len, void* state,
+                                         uint8_t* labels, int64_t label_block_stride, double* features_out,
+                                         int16_t* voiced, int64_t voiced_stride, int32_t* voiced_len,
+                                         const int32_t* frame_counts, uint8_t* restart, int32_t* init_left,
+                                         void* stream) {
+  return simple_stream_block_entry(frames, 2, block_stride, stream_stride, frame_len, fft_len, pad, band_bins,
+                                   n_streams, n_frames, noise_buf_len, state, labels, label_block_stride,
+                                   features_out, voiced, voiced_stride, voiced_len, true, frame_counts, restart,
+                                   init_left, stream);
 }
 
 size_t vad_scale_workspace_bytes(void) { return scale_workspace_bytes(); }

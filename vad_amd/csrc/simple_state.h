@@ -2,7 +2,8 @@
 // (realtime_analysis/simple_analyzer.py:78-112, 144-164, 245-256), one step
 // per feature row, for simple_stream_kernel.hip.  Both kernels there call
 // simple_state_step, so a stream gives the same labels and state whichever
-// way its rows were computed.
+// way its rows were computed; their sessions forms call simple_state_init_step
+// too, one definition of a joining stream's init for both paths.
 //
 // A stream's state in memory (include/vad_amd.h, vad_simple_stream_state_bytes):
 //   double noise[noise_buf_len][6]   energy, std|fft|, band 0..3 of the noise frames
@@ -145,6 +146,27 @@ __device__ __forceinline__ int simple_state_step(SimpleState& s, double* noise, 
     s.silence = 1;
   }
   return 1;
+}
+
+// One init frame of a stream that initialises itself (the sessions kernels):
+// load_init_inactive_frames (:120-138) a frame at a time.  The row fills noise
+// row nb - init_left; the last one (init_left 1 -> 0) makes the thresholds the
+// plain means and leaves what simple_stream_init_kernel leaves: status
+// cleared, silence on, noise_pointer 0, frame_number 0.
+__device__ __forceinline__ void simple_state_init_step(SimpleState& s, double* noise, int nb, int& init_left,
+                                                       const double* f) {
+#pragma clang fp contract(off)
+  double* row = noise + kSimpleNoiseCols * (nb - init_left);
+  row[0] = f[0];
+  row[1] = f[2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) row[2 + j] = f[3 + j];
+  if (--init_left > 0) return;
+  simple_noise_means(noise, nb, s.e_th, s.std_th, s.b_th);
+  s.status = 0;
+  s.silence = 1;
+  s.ptr = 0;
+  s.frame_no = 0;
 }
 
 }  // namespace vad

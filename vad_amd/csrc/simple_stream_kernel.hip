@@ -15,6 +15,12 @@
 //       in global memory: the second launch for every other L (after
 //       launch_simple_features), and the entry for hand-made rows.
 //   simple_stream_init_kernel      load_init_inactive_frames for all streams.
+//   simple_stream_block_sessions_kernel<T> / simple_stream_state_sessions_kernel
+//       the same two bodies built a second time (VAD_SIMPLE_SESSIONS 1): per
+//       stream a frame count, a restart flag the kernel consumes and the init
+//       frames it still owes, so callers join, leave and stall without a host
+//       step and a joining stream's load_init_inactive_frames is its first
+//       noise_buf_len frames (simple_state_init_step).
 //
 // No workgroup waits on another; there are no atomics.
 #include "simple_state.h"
@@ -59,70 +65,9 @@ struct SimpleBlockArgs {
 // is read one barrier after it is written, in the same two halves.
 template <typename T>
 __global__ __launch_bounds__(64 * kStreamBlockMaxWaves) void simple_stream_block_kernel(SimpleBlockArgs a) {
-  extern __shared__ __attribute__((aligned(16))) double ssm[];
-  const int L = a.L, nb = a.nb, K = a.n_frames;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int waves = blockDim.x >> 6;
-  double* twc = ssm;
-  double* tws = ssm + (L >> 1);
-  double* re = ssm + L + (size_t)wave * 2 * L;
-  double* im = re + L;
-  double* noise = ssm + L + (size_t)waves * 2 * L;
-  double* rows = noise + kSimpleNoiseCols * nb;
-  int* slot = reinterpret_cast<int*>(rows + 2 * waves * kFeatRow);
-  const int64_t s = blockIdx.x;
-  double* st = reinterpret_cast<double*>(static_cast<char*>(a.state) + s * simple_state_bytes(nb));
-  const T* frames = static_cast<const T*>(a.frames) + s * a.stream_stride;
-  T* voiced = a.voiced ? static_cast<T*>(a.voiced) + s * a.voiced_stride : nullptr;
-  int log2L = 0;
-  while ((1 << log2L) < L) ++log2L;
-  for (int j = threadIdx.x; j < (L >> 1); j += blockDim.x)
-    sincospi(-2.0 * (double)j / (double)L, &tws[j], &twc[j]);
-  for (int j = threadIdx.x; j < kSimpleNoiseCols * nb; j += blockDim.x) noise[j] = st[j];
-  SimpleState reg{};
-  if (threadIdx.x == 0) simple_state_load(reg, st, nb);
-  int n_voiced = 0;
-  __syncthreads();
-  const int rounds = (K + waves - 1) / waves;
-  for (int r = 0; r <= rounds; ++r) {
-    const int k = r * waves + wave;
-    if (r < rounds && k < K) {
-      double* o = rows + ((r & 1) * waves + wave) * kFeatRow;
-      simple_wave_features(frames + k * a.block_stride, a.frame_len, L, log2L, a.pad, a.band_bins, 4, 1, twc, tws,
-                           re, im, lane, o);
-      if (a.features_out && lane == 0) {
-        double* fo = a.features_out + ((int64_t)k * a.n_streams + s) * 7;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) fo[i] = o[i];
-      }
-      wave_lds_sync();  // the next round overwrites re / im
-    }
-    __syncthreads();
-    // the frames of round r - 1 that were labelled active, packed in order
-    const int kp = k - waves;
-    if (voiced && r > 0 && kp < K) {
-      const int at = slot[((r - 1) & 1) * waves + wave];
-      if (at >= 0) {
-        const T* x = frames + kp * a.block_stride;
-        T* d = voiced + (int64_t)at * a.frame_len;
-        for (int i = lane; i < a.frame_len; i += 64) d[i] = x[i];
-      }
-    }
-    if (threadIdx.x == 0 && r < rounds) {
-      for (int w = 0; w < waves && r * waves + w < K; ++w) {
-        const int lab = simple_state_step(reg, noise, nb, rows + ((r & 1) * waves + w) * kFeatRow);
-        a.labels[(int64_t)(r * waves + w) * a.lab_stride + s] = (uint8_t)lab;
-        slot[(r & 1) * waves + w] = lab ? n_voiced++ : -1;
-      }
-    }
-  }
-  // the last pass of the loop (r == rounds) was the barrier after the last steps
-  for (int j = threadIdx.x; j < kSimpleNoiseCols * nb; j += blockDim.x) st[j] = noise[j];
-  if (threadIdx.x == 0) {
-    simple_state_store(reg, st, nb);
-    if (a.voiced_len) a.voiced_len[s] = n_voiced * a.frame_len;
-  }
+#define VAD_SIMPLE_SESSIONS 0
+#include "simple_stream_block_body.inc"
+#undef VAD_SIMPLE_SESSIONS
 }
 
 // The state steps alone: one wave per stream, lane 0 stepping the rows
@@ -134,37 +79,9 @@ __global__ __launch_bounds__(256) void simple_stream_state_kernel(const double* 
                                                                   int64_t block_stride, int64_t stream_stride,
                                                                   int frame_len, float* voiced, int64_t voiced_stride,
                                                                   int32_t* voiced_len) {
-  const int lane = threadIdx.x & 63;
-  const int64_t s = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (s >= n_streams) return;
-  double* st = reinterpret_cast<double*>(static_cast<char*>(state) + s * simple_state_bytes(nb));
-  SimpleState reg{};
-  if (lane == 0) simple_state_load(reg, st, nb);
-  int n_voiced = 0;
-  for (int k = 0; k < n_frames; ++k) {
-    int lab = 0;
-    if (lane == 0) {
-      double f[7];
-      const double* row = feats + ((int64_t)k * n_streams + s) * 7;
-#pragma unroll
-      for (int i = 0; i < 7; ++i) f[i] = row[i];
-      lab = simple_state_step(reg, st, nb, f);
-      labels[(int64_t)k * lab_stride + s] = (uint8_t)lab;
-    }
-    if (voiced) {
-      lab = __shfl(lab, 0);
-      if (lab) {
-        const float* x = frames + k * block_stride + s * stream_stride;
-        float* d = voiced + s * voiced_stride + (int64_t)n_voiced * frame_len;
-        for (int i = lane; i < frame_len; i += 64) d[i] = x[i];
-        ++n_voiced;
-      }
-    }
-  }
-  if (lane == 0) {
-    simple_state_store(reg, st, nb);
-    if (voiced_len) voiced_len[s] = n_voiced * frame_len;
-  }
+#define VAD_SIMPLE_SESSIONS 0
+#include "simple_stream_state_body.inc"
+#undef VAD_SIMPLE_SESSIONS
 }
 
 // load_init_inactive_frames (:120-138) for every stream, one lane each: the
@@ -189,6 +106,35 @@ __global__ __launch_bounds__(256) void simple_stream_init_kernel(const double* _
   simple_state_store(reg, st, nb);
 }
 
+// The sessions forms.  Per stream: frame_counts[s] frames of its column are
+// taken (clamped to 0..n_frames), a nonzero restart[s] makes it fresh first
+// (record zero, init_left = nb) and is stored back 0, init_left[s] init frames
+// are still owed.  Label rows of init frames hold VAD_LABEL_INIT, rows past
+// the count VAD_LABEL_NO_HOP; a stream with no frame and no restart writes
+// nothing else but voiced_len 0.
+struct SimpleSessions {
+  const int32_t* frame_counts;
+  uint8_t* restart;
+  int32_t* init_left;
+};
+
+template <typename T>
+__global__ __launch_bounds__(64 * kStreamBlockMaxWaves) void simple_stream_block_sessions_kernel(SimpleBlockArgs a,
+                                                                                                  SimpleSessions ss) {
+#define VAD_SIMPLE_SESSIONS 1
+#include "simple_stream_block_body.inc"
+#undef VAD_SIMPLE_SESSIONS
+}
+
+__global__ __launch_bounds__(256) void simple_stream_state_sessions_kernel(
+    const double* __restrict__ feats, int64_t n_streams, int n_frames, int nb, void* state, uint8_t* labels,
+    int64_t lab_stride, const float* frames, int64_t block_stride, int64_t stream_stride, int frame_len, float* voiced,
+    int64_t voiced_stride, int32_t* voiced_len, SimpleSessions ss) {
+#define VAD_SIMPLE_SESSIONS 1
+#include "simple_stream_state_body.inc"
+#undef VAD_SIMPLE_SESSIONS
+}
+
 // Waves of a block-kernel workgroup: up to 4, as many as the LDS holds beside
 // the twiddle table, and no more than there are frames.
 static int stream_block_waves(int L, int nb, int n_frames) {
@@ -200,40 +146,55 @@ static int stream_block_waves(int L, int nb, int n_frames) {
 bool simple_stream_block_fits(int L) { return L >= 2 && L <= 4096 && (L & (L - 1)) == 0; }
 
 template <typename T>
-static hipError_t launch_block(const SimpleBlockArgs& a, hipStream_t st) {
+static hipError_t launch_block(const SimpleBlockArgs& a, const SimpleSessions* ss, hipStream_t st) {
   const int waves = stream_block_waves(a.L, a.nb, a.n_frames);
   const size_t smem = stream_block_doubles(a.L, waves, a.nb) * sizeof(double);
   if (smem > (size_t)kStreamBlockLds) return hipErrorInvalidValue;
-  static std::atomic<unsigned long long> attr_done{0};
-  hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&simple_stream_block_kernel<T>), kStreamBlockLds,
-                                attr_done);
+  static std::atomic<unsigned long long> attr_done{0}, attr_done_ss{0};
+  const void* fn = ss ? reinterpret_cast<const void*>(&simple_stream_block_sessions_kernel<T>)
+                      : reinterpret_cast<const void*>(&simple_stream_block_kernel<T>);
+  hipError_t e = ensure_dyn_lds(fn, kStreamBlockLds, ss ? attr_done_ss : attr_done);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(simple_stream_block_kernel<T>, dim3((unsigned)a.n_streams), dim3(64 * waves), smem, st, a);
+  if (ss)
+    hipLaunchKernelGGL(simple_stream_block_sessions_kernel<T>, dim3((unsigned)a.n_streams), dim3(64 * waves), smem,
+                       st, a, *ss);
+  else
+    hipLaunchKernelGGL(simple_stream_block_kernel<T>, dim3((unsigned)a.n_streams), dim3(64 * waves), smem, st, a);
   return hipGetLastError();
 }
 
 hipError_t launch_simple_stream_block(const void* frames, int in_bytes, int64_t block_stride, int64_t stream_stride,
                                       int frame_len, int L, int pad, int band_bins, int64_t n_streams, int n_frames,
                                       int nb, void* state, uint8_t* labels, int64_t lab_stride, double* features_out,
-                                      void* voiced, int64_t voiced_stride, int32_t* voiced_len, hipStream_t st) {
+                                      void* voiced, int64_t voiced_stride, int32_t* voiced_len,
+                                      const int32_t* frame_counts, uint8_t* restart, int32_t* init_left,
+                                      hipStream_t st) {
   if (n_streams <= 0 || n_frames <= 0) return hipSuccess;
   if (!simple_stream_block_fits(L) || n_streams > 0x7fffffff) return hipErrorInvalidValue;
   SimpleBlockArgs a{frames, block_stride, stream_stride, frame_len, L,      pad,          band_bins,     n_frames,
                     nb,     n_streams,    state,         labels,    lab_stride, features_out, voiced, voiced_stride,
                     voiced_len};
-  return in_bytes == 2 ? launch_block<int16_t>(a, st) : launch_block<float>(a, st);
+  const SimpleSessions ss{frame_counts, restart, init_left};
+  const SimpleSessions* p = frame_counts ? &ss : nullptr;  // all three or none (the C entries have checked)
+  return in_bytes == 2 ? launch_block<int16_t>(a, p, st) : launch_block<float>(a, p, st);
 }
 
 hipError_t launch_simple_stream_state(const double* feats, int64_t n_streams, int n_frames, int nb, void* state,
                                       uint8_t* labels, int64_t lab_stride, const float* frames, int64_t block_stride,
                                       int64_t stream_stride, int frame_len, float* voiced, int64_t voiced_stride,
-                                      int32_t* voiced_len, hipStream_t st) {
+                                      int32_t* voiced_len, const int32_t* frame_counts, uint8_t* restart,
+                                      int32_t* init_left, hipStream_t st) {
   if (n_streams <= 0 || n_frames <= 0) return hipSuccess;
   const int64_t blocks = (n_streams + 3) / 4;
   if (blocks > 0x7fffffff) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(simple_stream_state_kernel, dim3((unsigned)blocks), dim3(256), 0, st, feats, n_streams, n_frames,
-                     nb, state, labels, lab_stride, frames, block_stride, stream_stride, frame_len, voiced,
-                     voiced_stride, voiced_len);
+  if (frame_counts)
+    hipLaunchKernelGGL(simple_stream_state_sessions_kernel, dim3((unsigned)blocks), dim3(256), 0, st, feats, n_streams,
+                       n_frames, nb, state, labels, lab_stride, frames, block_stride, stream_stride, frame_len, voiced,
+                       voiced_stride, voiced_len, SimpleSessions{frame_counts, restart, init_left});
+  else
+    hipLaunchKernelGGL(simple_stream_state_kernel, dim3((unsigned)blocks), dim3(256), 0, st, feats, n_streams,
+                       n_frames, nb, state, labels, lab_stride, frames, block_stride, stream_stride, frame_len, voiced,
+                       voiced_stride, voiced_len);
   return hipGetLastError();
 }
 

@@ -298,15 +298,20 @@ hipError_t launch_simple_features(const float* frames, int64_t n_frames, int fra
 // Streams of that analyser (simple_stream_kernel.hip).  The C entries have
 // checked every argument.  simple_stream_block_fits: L is one the block
 // kernel takes (a power of two <= 4096); in_bytes 4 / 2: fp32 / int16 frames.
+// frame_counts / restart / init_left: all three for the sessions kernels, all
+// null for the plain ones.
 bool simple_stream_block_fits(int L);
 hipError_t launch_simple_stream_block(const void* frames, int in_bytes, int64_t block_stride, int64_t stream_stride,
                                       int frame_len, int L, int pad, int band_bins, int64_t n_streams, int n_frames,
                                       int nb, void* state, uint8_t* labels, int64_t lab_stride, double* features_out,
-                                      void* voiced, int64_t voiced_stride, int32_t* voiced_len, hipStream_t st);
+                                      void* voiced, int64_t voiced_stride, int32_t* voiced_len,
+                                      const int32_t* frame_counts, uint8_t* restart, int32_t* init_left,
+                                      hipStream_t st);
 hipError_t launch_simple_stream_state(const double* feats, int64_t n_streams, int n_frames, int nb, void* state,
                                       uint8_t* labels, int64_t lab_stride, const float* frames, int64_t block_stride,
                                       int64_t stream_stride, int frame_len, float* voiced, int64_t voiced_stride,
-                                      int32_t* voiced_len, hipStream_t st);
+                                      int32_t* voiced_len, const int32_t* frame_counts, uint8_t* restart,
+                                      int32_t* init_left, hipStream_t st);
 hipError_t launch_simple_stream_init(const double* feats, int64_t n_streams, int nb, void* state, hipStream_t st);
 size_t scale_workspace_bytes();
 hipError_t launch_scale_features(float* x, int64_t n_rows, int mfcc_n, double* ws, hipStream_t st);

@@ -20,6 +20,37 @@ valid: vad.py:52-57's ``active_frames += np_frame.tobytes()``.
 
 The state layout is include/vad_amd.h's; ``analyser(s)`` / ``from_analysers``
 move a stream to and from the single-stream host class.
+
+Sessions (``sessions=True``): callers that join, leave and stall, without a
+host step.  Every block reads three static per-stream tensors inside the
+kernel (vad_simple_stream_block_sessions_f32 / _i16, and
+vad_simple_stream_state_sessions on the two-launch path):
+
+* ``frame_counts`` (S,) int32, initially K: stream s takes
+  ``min(max(frame_counts[s], 0), k)`` frames, the first rows of its column of
+  the k-frame block.
+* ``restart`` (S,) uint8: nonzero makes the stream fresh before its frames of
+  this block; the kernel stores 0 back, so a flag set once restarts once,
+  also when a captured graph is replayed.
+* ``init_left`` (S,) int32: the frames a stream still needs before it is
+  initialised.  A fresh stream has an all-zero state record and
+  ``init_left = noise_buf_len``; a sessions batch starts with every stream
+  fresh and never raises "Analyser not initialized".
+
+A fresh stream's next noise_buf_len frames are its init frames, whichever
+blocks they arrive in: vad.py:45-49 per caller, on the device.  Each one's
+feature row fills a noise row, and the last does what
+``load_init_inactive_frames`` does on those frames (thresholds the plain
+means, status cleared, silence on); frames after it in the same block are
+classified.  Init frames are labelled ``LABEL_INIT`` (253) and never packed
+into ``voiced``; label rows past a stream's count hold ``LABEL_NO_HOP`` (254)
+and its ``features`` rows there are not written (the two-launch path computes
+every row).  ``voiced_len`` counts the frames labelled 1.  A stream with no
+frame and no restart keeps every byte of its state and its ``init_left``; a
+restart with no frame leaves the stream fresh.  With every count k, no restart
+and every ``init_left`` 0 (after ``load_init_inactive_frames`` or
+``from_analysers``, which set it) a sessions batch computes what a plain one
+does, bit for bit.
 """
 from __future__ import annotations
 
@@ -35,6 +66,8 @@ from .stream import hop_rows_disjoint
 
 STATUS_BITS = SimpleAnalyser.TEMP_BUFFER_SIZE
 N_FEATS = 7
+LABEL_NO_HOP = _lib.LABEL_NO_HOP  # VAD_LABEL_NO_HOP: a label row the stream has no frame in (sessions)
+LABEL_INIT = _lib.LABEL_INIT      # VAD_LABEL_INIT: a label row that holds one of the stream's init frames (sessions)
 NOISE_COLS = 6                    # energy, std, band 0..3
 _NOISE_FROM_FEAT = [0, 2, 3, 4, 5, 6]  # columns of a feature row kept in a noise row
 
@@ -65,10 +98,12 @@ class SimpleStreamBatch:
     """S SimpleAnalyser streams advanced ``frames_per_step`` frames per call.
 
     ``features=True`` keeps the rows the kernel classified in ``features``
-    (K, S, 7) float64 (always kept where the two-launch path needs them)."""
+    (K, S, 7) float64 (always kept where the two-launch path needs them).
+    ``sessions=True``: per-stream frame counts, restarts and in-kernel
+    initialisation (the module docstring has the rules)."""
 
     def __init__(self, n_streams, frame_rate, frame_size, noise_buf_len, frames_per_step=1,
-                 input_dtype=torch.float32, voiced=False, device=None, features=False):
+                 input_dtype=torch.float32, voiced=False, device=None, features=False, sessions=False):
         S, K, nb = int(n_streams), int(frames_per_step), int(noise_buf_len)
         if S < 1:
             raise ValueError("n_streams must be >= 1")
@@ -107,9 +142,16 @@ class SimpleStreamBatch:
             if features or not self.one_kernel else None
         self.voiced = torch.zeros((S, K * frame_size), dtype=input_dtype, device=dev) if voiced else None
         self.voiced_len = torch.zeros((S,), dtype=torch.int32, device=dev) if voiced else None
-        self.initialized = False
+        self.sessions = bool(sessions)
+        self.frame_counts = self.restart = self.init_left = None
+        if self.sessions:  # static: a captured graph reads them in place
+            self.frame_counts = torch.full((S,), K, dtype=torch.int32, device=dev)
+            self.restart = torch.zeros((S,), dtype=torch.uint8, device=dev)
+            self.init_left = torch.full((S,), nb, dtype=torch.int32, device=dev)  # every stream fresh
+        self.initialized = self.sessions  # each stream of a sessions batch initialises itself
         self.graph = None
-        self._fn_name = "vad_simple_stream_block_i16" if self._i16 else "vad_simple_stream_block_f32"
+        self._fn_name = "vad_simple_stream_block" + ("_sessions" if self.sessions else "") + \
+            ("_i16" if self._i16 else "_f32")
         self._fn = None
 
     # -- state views (read-only: they alias the device state) -------------------
@@ -172,15 +214,39 @@ class SimpleStreamBatch:
         feats = self._frame_features(frames.reshape(-1, self.frame_size))
         _lib.check(_lib.lib().vad_simple_stream_init(_lib.ptr(feats), self.n, self.noise_buf_len, _lib.ptr(self.state),
                                                      _lib.stream_ptr()), "vad_simple_stream_init")
+        if self.sessions:
+            self.init_left.zero_()
         self.initialized = True
 
     def reset(self):
-        """Back to a batch before load_init_inactive_frames."""
+        """Back to a batch before load_init_inactive_frames (sessions: every
+        stream fresh, the counts K, no restart pending)."""
         self.state.zero_()
         self.label_block.zero_()
         if self.voiced_len is not None:
             self.voiced_len.zero_()
-        self.initialized = False
+        if self.sessions:
+            self.frame_counts.fill_(self.K)
+            self.restart.zero_()
+            self.init_left.fill_(self.noise_buf_len)
+        self.initialized = self.sessions
+
+    def _set_sessions(self, frame_counts, restart):
+        """Check the per-call tensors and copy them into the static ones."""
+        if frame_counts is None and restart is None:
+            return
+        if not self.sessions:
+            raise ValueError("frame_counts / restart: build the batch with sessions=True")
+        for t, dst, name in ((frame_counts, self.frame_counts, "frame_counts"), (restart, self.restart, "restart")):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.shape != dst.shape or t.dtype != dst.dtype:
+                raise ValueError(f"{name} must be a CUDA {str(dst.dtype).replace('torch.', '')} tensor of shape "
+                                 f"{tuple(dst.shape)}")
+        if frame_counts is not None:
+            self.frame_counts.copy_(frame_counts)
+        if restart is not None:
+            self.restart.copy_(restart)
 
     def _check_frame_size(self, frames):
         if frames.shape[-1] != self.frame_size:
@@ -195,6 +261,8 @@ class SimpleStreamBatch:
             self._head = (L, self.fft_len, self.fft_extended_zeros, self.fftn_for_band, self.n)
             self._tail = (self.noise_buf_len, _lib.ptr(self.state), _lib.ptr(self.label_block), self.n,
                           _lib.ptr(self.features), _lib.ptr(self.voiced), self.K * L, _lib.ptr(self.voiced_len))
+            if self.sessions:
+                self._tail += (_lib.ptr(self.frame_counts), _lib.ptr(self.restart), _lib.ptr(self.init_left))
         rc = self._fn(ctypes.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), *self._head, k, *self._tail,
                       _lib.stream_ptr() if stream is None else stream)
         if rc:
@@ -203,12 +271,15 @@ class SimpleStreamBatch:
     def _block_body(self):
         self._launch(self.inputs, self.K)
 
-    def step_block(self, frames=None):
+    def step_block(self, frames=None, frame_counts=None, restart=None):
         """Advance every stream by a block of frames: (k, S, frame_size) of the
         batch's input dtype on the device, k <= frames_per_step (a short block
         is the tail of a sequence), or None for the K frames already written
         into ``inputs``.  Returns the static label_block (its first k rows
-        for a short block)."""
+        for a short block).  sessions: frame_counts (S,) int32 / restart (S,)
+        uint8 CUDA tensors are copied into the static ones first; None leaves
+        those as written."""
+        self._set_sessions(frame_counts, restart)
         if not self.initialized:
             raise Exception("Analyser not initialized")
         k = self.K
@@ -231,11 +302,13 @@ class SimpleStreamBatch:
             self._launch(self.inputs, k)
         return self.label_block if k == self.K else self.label_block[:k]
 
-    def step(self, frames=None):
+    def step(self, frames=None, frame_counts=None, restart=None):
         """One frame of every stream: (S, frame_size), or None for the frame in
-        ``inputs[0]``.  frames_per_step == 1.  Returns ``labels`` (S,)."""
+        ``inputs[0]``.  frames_per_step == 1.  Returns ``labels`` (S,).
+        frame_counts / restart: as for step_block."""
         if self.K != 1:
             raise ValueError("this batch advances frames_per_step frames at a time: use step_block")
+        self._set_sessions(frame_counts, restart)
         if frames is not None:
             if not self.initialized:
                 raise Exception("Analyser not initialized")
@@ -253,8 +326,9 @@ class SimpleStreamBatch:
             raise Exception("Analyser not initialized")
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        keep = [t for t in (self.state, self.label_block, self.features, self.voiced, self.voiced_len)
-                if t is not None]
+        # sessions: the warm-up consumes restart flags and init frames
+        keep = [t for t in (self.state, self.label_block, self.features, self.voiced, self.voiced_len,
+                            self.frame_counts, self.restart, self.init_left) if t is not None]
         saved = [t.clone() for t in keep]
         with torch.cuda.stream(s):
             self._block_body()  # warm-up (first launch sets kernel attributes)
@@ -302,14 +376,15 @@ class SimpleStreamBatch:
         sa.silence = bool(w[1])
         sa.noise_pointer = int(w[2])
         sa.frame_number = int(w[3])
-        sa.initialized = self.initialized
+        sa.initialized = int(self.init_left[s]) == 0 if self.sessions else self.initialized
         return sa
 
     @classmethod
     def from_analysers(cls, analysers, frames_per_step=1, input_dtype=torch.float32, voiced=False, device=None,
-                       features=False):
+                       features=False, sessions=False):
         """A batch whose stream s continues analysers[s] (initialised
-        SimpleAnalyser objects of one frame rate, frame size and noise_buf_len)."""
+        SimpleAnalyser objects of one frame rate, frame size and noise_buf_len);
+        with sessions=True every stream's init_left is 0."""
         analysers = list(analysers)
         if not analysers:
             raise ValueError("no analysers")
@@ -320,8 +395,10 @@ class SimpleStreamBatch:
             if not a.initialized:
                 raise Exception("Analyser not initialized")
         sb = cls(len(analysers), a0.frame_rate, a0.frame_size, a0.noise_buf_len, frames_per_step=frames_per_step,
-                 input_dtype=input_dtype, voiced=voiced, device=device, features=features)
+                 input_dtype=input_dtype, voiced=voiced, device=device, features=features, sessions=sessions)
         sb.state.copy_(torch.from_numpy(pack_state(analysers)))
+        if sb.sessions:
+            sb.init_left.zero_()
         sb.initialized = True
         return sb
 
