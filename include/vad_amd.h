@@ -358,6 +358,56 @@ int vad_tree_train(const float* x, const uint8_t* y, int64_t n_rows, int32_t n_f
                    const int32_t* order, const uint8_t* mask, int32_t n_jobs, const vad_tree_job* jobs,
                    const vad_tree_tables* tables, void* workspace, size_t workspace_bytes, int32_t* n_levels,
                    void* stream);
+/* vad_tree_train with a feature subset per job (a forest's max_features in
+ * its per-tree form): feature_masks[j] (host, n_jobs words) has bit f set when
+ * job j may split on feature f; NULL: every job may use every feature, and
+ * the call is vad_tree_train.  A feature whose bit is clear contributes no
+ * candidate to the job's nodes; the rule is otherwise unchanged (the largest
+ * score, then the lowest allowed feature, then the lowest position), so job j
+ * grows the tree of its rows restricted to its columns.  A job none of whose
+ * allowed features can split is a single leaf.  VAD_EINVAL before any HIP
+ * call: a mask with no bit below n_features set. */
+int vad_tree_train_features(const float* x, const uint8_t* y, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                            const int32_t* order, const uint8_t* mask, const uint64_t* feature_masks, int32_t n_jobs,
+                            const vad_tree_job* jobs, const vad_tree_tables* tables, void* workspace,
+                            size_t workspace_bytes, int32_t* n_levels, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Random forest: n_trees decision trees in one node table, their leaf class
+ * shares averaged -- predict_proba / predict of sklearn's
+ * RandomForestClassifier, ExtraTreesClassifier and BaggingClassifier over
+ * decision trees with n_jobs = 1.  Per row, n_classes double accumulators
+ * start at 0; for t = 0 .. n_trees-1 in order acc[k] += proba[leaf_t][k];
+ * then acc[k] /= n_trees.  The score is (float)acc[active], the label the
+ * first maximum of acc (a class index).  The walk is vad_tree_plan's.
+ *
+ * The node arrays are vad_tree_plan_create's (host), the trees one after
+ * another: tree t is the nodes [roots[t], roots[t + 1]) (the last tree ends
+ * at n_nodes), its root first; roots[0] = 0, roots ascending; left / right are
+ * indices into the whole table and must stay inside their tree.  proba[i *
+ * n_classes + k] (host, float64) is node i's share of class k (the rows of
+ * leaves are read).  Limits: n_trees >= 1, 1 <= n_classes <= 8, n_nodes <=
+ * 2^24, n_features <= 64; anything else, a root outside the table included,
+ * is VAD_EINVAL before any HIP call.
+ *
+ * vad_forest_predict: rows x[i*n_features + f].  vad_features_forest: every
+ * window of an MFCC sequence, as vad_features_tree (a clip's rows or a packed
+ * clip batch's), the features of a window computed once for all trees.
+ * labels[i] always, scores[i] when scores is not NULL.  VAD_EINVAL: a NULL
+ * forest / input / labels, n or n_frames < 0, active outside 0 .. n_classes-1,
+ * outputs that overlap the input or each other.
+ * ------------------------------------------------------------------------- */
+#define VAD_FOREST_MAX_CLASSES 8
+typedef struct vad_forest vad_forest;
+
+int vad_forest_create(int32_t n_nodes, const int32_t* feature, const double* threshold, const int32_t* left,
+                      const int32_t* right, const uint8_t* nan_left, int32_t n_trees, const int32_t* roots,
+                      int32_t n_classes, const double* proba, int32_t n_features, vad_forest** out);
+int vad_forest_destroy(vad_forest* forest);
+int vad_forest_predict(const vad_forest* forest, const float* x, int64_t n, int32_t active, uint8_t* labels,
+                       float* scores, void* stream);
+int vad_features_forest(const vad_forest* forest, const float* mfcc, int64_t n_frames, int32_t mfcc_n, int32_t mode,
+                        int32_t active, uint8_t* labels, float* scores, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Offline dataset export (dataset_creator.py:58-66 -> file_processing.py,

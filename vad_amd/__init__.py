@@ -21,6 +21,10 @@ def __getattr__(name):
     if name == "SimpleStreamBatch":
         from .simple_stream import SimpleStreamBatch
         return SimpleStreamBatch
+    # the forest needs torch: imported on first use
+    if name == "ForestClassifier":
+        from .forest import ForestClassifier
+        return ForestClassifier
     # the resamplers load the built library on first use
     if name in ("Resampler", "StreamResampler", "SessionStreamResampler", "resample_clips", "resample_model",
                 "ResampleSpec"):

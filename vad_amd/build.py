@@ -20,7 +20,8 @@ SOURCES = ["capi.hip", "mfcc_kernel.hip", "ffn_kernel.hip", "tree_kernel.hip",
            "dataset_kernel.hip", "csv_format.hip", "simple_kernel.hip", "stream_kernel.hip", "rccl.hip",
            "spec_generic.hip", "segments_kernel.hip", "stream_segments_kernel.hip", "train_kernel.hip",
            "tree_train_kernel.hip", "stream_tree_kernel.hip", "csv_parse_kernel.hip", "batch_kernel.hip",
-           "batch_segments_kernel.hip", "simple_stream_kernel.hip", "resample_kernel.hip", "score_kernel.hip"]
+           "batch_segments_kernel.hip", "simple_stream_kernel.hip", "resample_kernel.hip", "score_kernel.hip",
+           "forest_kernel.hip"]
 # per-translation-unit code-generation flags: the FFT's packed-fp32 chains
 # run ~5% faster under the ILP-oriented machine scheduler (fewer dependent
 # pairs back to back, i.e. fewer hazard s_nops and stalls)
@@ -46,6 +47,7 @@ UNIT_FLAGS = {
     "simple_stream_kernel.hip": [],
     "resample_kernel.hip": [],
     "score_kernel.hip": [],
+    "forest_kernel.hip": [],
 }
 
 

@@ -788,6 +788,132 @@ int vad_features_tree_scores(const vad_tree_plan* t, const float* node_score, co
                                         mode, scores, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------
+// Random forest (forest_kernel.hip)
+// ---------------------------------------------------------------------------
+struct vad_forest {
+  TreeNode* nodes_dev;
+  TreeNodeC* cnodes_dev;  // compact copy for the LDS-resident window walk
+  int* roots_dev;         // n_trees + 1
+  double* proba_dev;      // (n_nodes, n_classes)
+  int n_nodes;
+  int n_trees;
+  int n_classes;
+  int n_features;
+  int max_lds_tree;  // nodes of the largest tree the window kernel stages in LDS
+};
+
+int vad_forest_create(int32_t n_nodes, const int32_t* feature, const double* threshold, const int32_t* left,
+                      const int32_t* right, const uint8_t* nan_left, int32_t n_trees, const int32_t* roots,
+                      int32_t n_classes, const double* proba, int32_t n_features, vad_forest** out) {
+  if (!feature || !threshold || !left || !right || !roots || !proba || !out || n_nodes <= 0 || n_features <= 0 ||
+      n_trees < 1 || n_classes < 1 || n_classes > VAD_FOREST_MAX_CLASSES)
+    return VAD_EINVAL;
+  if (n_nodes > (1 << 24) || n_features > 3 * VAD_MAX_MFCC + 16) return VAD_EUNSUPPORTED;
+  if (n_trees > n_nodes || roots[0] != 0) return VAD_EINVAL;
+  for (int t = 1; t < n_trees; ++t)
+    if (roots[t] <= roots[t - 1] || roots[t] >= n_nodes) return VAD_EINVAL;
+  std::vector<int> r(roots, roots + n_trees);
+  r.push_back(n_nodes);
+  std::vector<TreeNode> h((size_t)n_nodes);
+  std::vector<TreeNodeC> c((size_t)n_nodes);
+  int max_lds_tree = 0;
+  for (int t = 0; t < n_trees; ++t) {
+    const int lo = r[t], hi = r[t + 1];
+    if (hi - lo <= 3072 && hi - lo > max_lds_tree) max_lds_tree = hi - lo;  // kLdsNodes of the tree kernels
+    for (int i = lo; i < hi; ++i) {
+      TreeNode& nd = h[i];
+      nd.feature = feature[i] >= 0 ? feature[i] : -1;
+      nd.threshold = threshold[i];
+      nd.leaf = 0;
+      nd.nan_left = (short)(nan_left ? (nan_left[i] != 0) : 0);
+      nd.left = nd.right = -1;
+      TreeNodeC& cn = c[i];
+      cn.thr = 0.f;
+      cn.feature = -1;
+      cn.left = cn.right = -1;
+      if (nd.feature < 0) continue;
+      // internal: the children inside the tree and past its root, the feature in the row
+      if (nd.feature >= n_features || left[i] <= lo || left[i] >= hi || right[i] <= lo || right[i] >= hi)
+        return VAD_EINVAL;
+      nd.left = left[i] - lo;
+      nd.right = right[i] - lo;
+      float f = (float)nd.threshold;  // round down to a float: x <= f  <=>  (double)x <= threshold
+      if ((double)f > nd.threshold) f = nextafterf(f, -INFINITY);
+      cn.thr = f;
+      cn.feature = nd.feature | (nd.nan_left ? 1 << 30 : 0);
+      cn.left = nd.left;
+      cn.right = nd.right;
+    }
+  }
+  vad_forest* p = (vad_forest*)calloc(1, sizeof(vad_forest));
+  if (!p) return VAD_ENOMEM;
+  const size_t pb = (size_t)n_nodes * (size_t)n_classes * sizeof(double);
+  hipError_t e = hipMalloc((void**)&p->nodes_dev, h.size() * sizeof(TreeNode));
+  if (e == hipSuccess) e = hipMalloc((void**)&p->cnodes_dev, c.size() * sizeof(TreeNodeC));
+  if (e == hipSuccess) e = hipMalloc((void**)&p->roots_dev, r.size() * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&p->proba_dev, pb);
+  if (e == hipSuccess) e = hipMemcpy(p->nodes_dev, h.data(), h.size() * sizeof(TreeNode), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(p->cnodes_dev, c.data(), c.size() * sizeof(TreeNodeC), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(p->roots_dev, r.data(), r.size() * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(p->proba_dev, proba, pb, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    vad_forest_destroy(p);
+    return (int)e;
+  }
+  p->n_nodes = n_nodes;
+  p->n_trees = n_trees;
+  p->n_classes = n_classes;
+  p->n_features = n_features;
+  p->max_lds_tree = max_lds_tree;
+  *out = p;
+  return VAD_OK;
+}
+
+int vad_forest_destroy(vad_forest* p) {
+  if (!p) return VAD_OK;
+  if (p->nodes_dev) (void)hipFree(p->nodes_dev);
+  if (p->cnodes_dev) (void)hipFree(p->cnodes_dev);
+  if (p->roots_dev) (void)hipFree(p->roots_dev);
+  if (p->proba_dev) (void)hipFree(p->proba_dev);
+  free(p);
+  return VAD_OK;
+}
+
+static ForestDev forest_dev(const vad_forest* p) {
+  return ForestDev{p->nodes_dev, p->cnodes_dev, p->roots_dev, p->proba_dev, p->n_trees, p->n_classes};
+}
+
+int vad_forest_predict(const vad_forest* f, const float* x, int64_t n, int32_t active, uint8_t* labels, float* scores,
+                       void* stream) {
+  if (!f || n < 0 || active < 0 || active >= f->n_classes) return VAD_EINVAL;
+  if (n == 0) return VAD_OK;
+  if (!x || !labels) return VAD_EINVAL;
+  if (n > INT64_MAX / 4 / f->n_features) return VAD_EINVAL;
+  const size_t xb = (size_t)n * f->n_features * 4;
+  if (overlap(x, xb, labels, (size_t)n) || overlap(x, xb, scores, scores ? (size_t)n * 4 : 0) ||
+      overlap(labels, (size_t)n, scores, scores ? (size_t)n * 4 : 0))
+    return VAD_EINVAL;
+  return (int)launch_forest_rows(forest_dev(f), x, n, f->n_features, active, labels, scores, (hipStream_t)stream);
+}
+
+int vad_features_forest(const vad_forest* f, const float* mfcc, int64_t n_frames, int32_t mfcc_n, int32_t mode,
+                        int32_t active, uint8_t* labels, float* scores, void* stream) {
+  if (!f || n_frames < 0 || mfcc_n <= 0 || mfcc_n > VAD_MAX_MFCC || (mode != 0 && mode != 1) || active < 0 ||
+      active >= f->n_classes)
+    return VAD_EINVAL;
+  if (f->n_features > 3 * mfcc_n) return VAD_EINVAL;
+  const int64_t rows = n_frames > 5 ? n_frames - 5 : 0;
+  if (rows == 0) return VAD_OK;
+  if (!mfcc || !labels || n_frames > INT64_MAX / 64) return VAD_EINVAL;
+  const size_t mb = (size_t)n_frames * mfcc_n * 4;
+  if (overlap(mfcc, mb, labels, (size_t)rows) || overlap(mfcc, mb, scores, scores ? (size_t)rows * 4 : 0) ||
+      overlap(labels, (size_t)rows, scores, scores ? (size_t)rows * 4 : 0))
+    return VAD_EINVAL;
+  return (int)launch_forest_windows(forest_dev(f), f->max_lds_tree, mfcc, rows, mfcc_n, mode, active, labels, scores,
+                                    (hipStream_t)stream);
+}
+
 int vad_simple_features(const float* frames, int64_t n_frames, int32_t frame_len,
                         int64_t frame_stride, int32_t fft_len, int32_t pad, int32_t band_bins,
                         int32_t n_bands, double* out, void* stream) {
@@ -1127,7 +1253,20 @@ int vad_tree_train(const float* x, const uint8_t* y, int64_t n_rows, int32_t n_f
                    const int32_t* order, const uint8_t* mask, int32_t n_jobs, const vad_tree_job* jobs,
                    const vad_tree_tables* tables, void* workspace, size_t workspace_bytes, int32_t* n_levels,
                    void* stream) {
+  return vad_tree_train_features(x, y, n_rows, n_features, n_classes, order, mask, nullptr, n_jobs, jobs, tables,
+                                 workspace, workspace_bytes, n_levels, stream);
+}
+
+int vad_tree_train_features(const float* x, const uint8_t* y, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                            const int32_t* order, const uint8_t* mask, const uint64_t* feature_masks, int32_t n_jobs,
+                            const vad_tree_job* jobs, const vad_tree_tables* tables, void* workspace,
+                            size_t workspace_bytes, int32_t* n_levels, void* stream) {
   if (!tree_train_shape_ok(n_rows, n_features, n_classes, n_jobs, jobs)) return VAD_EINVAL;
+  if (feature_masks) {  // every job needs a feature it may split on
+    const uint64_t all = n_features == 64 ? ~0ull : (1ull << n_features) - 1;
+    for (int j = 0; j < n_jobs; ++j)
+      if (!(feature_masks[j] & all)) return VAD_EINVAL;
+  }
   if (!x || !y || !order || !tables || !workspace) return VAD_EINVAL;
   const vad_tree_tables& t = *tables;
   if (!t.feature || !t.threshold || !t.left || !t.right || !t.leaf || !t.nan_left || !t.n_node_samples || !t.depth ||
@@ -1140,8 +1279,8 @@ int vad_tree_train(const float* x, const uint8_t* y, int64_t n_rows, int32_t n_f
   const size_t need = tree_train_ws_bytes(n_rows, n_features, n_jobs, jobs);
   if (need == 0) return VAD_EUNSUPPORTED;
   if (workspace_bytes < need) return VAD_EINVAL;
-  return tree_train_run(x, y, n_rows, n_features, n_classes, order, mask, n_jobs, jobs, t, workspace, workspace_bytes,
-                        n_levels, (hipStream_t)stream);
+  return tree_train_run(x, y, n_rows, n_features, n_classes, order, mask, feature_masks, n_jobs, jobs, t, workspace,
+                        workspace_bytes, n_levels, (hipStream_t)stream);
 }
 
 size_t vad_mfcc_ffn_workspace_bytes(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, int64_t n_samples,

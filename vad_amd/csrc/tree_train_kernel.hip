@@ -315,12 +315,16 @@ __global__ __launch_bounds__(kTT) void tt_class_tiles(const uint2* __restrict__ 
         (unsigned)(tot[threadIdx.x >> 2] >> (16 * (threadIdx.x & 3))) & 0xffffu;
 }
 
-// NW: 64-bit words of packed 16-bit class counters (1: up to 4 classes)
-template <int NW>
+// NW: 64-bit words of packed 16-bit class counters (1: up to 4 classes).
+// MASKED: jfmask[job] has bit f set when the job may split on feature f
+// (vad_tree_train_features); a feature whose bit is clear in a segment's job
+// mask contributes no candidate to that segment, and a feature no segment of
+// the tile may use is not searched at all.  !MASKED is the kernel as it was.
+template <int NW, bool MASKED>
 __global__ __launch_bounds__(kTT) void tt_search(const uint2* __restrict__ list, int Tp, int Tl, int F, int fc,
                                                  const unsigned* __restrict__ tilecnt, int NT, Segs sg, int S,
-                                                 const int* __restrict__ jmsl, Rec* __restrict__ segbest, int Smax,
-                                                 Rec* __restrict__ tilefirst) {
+                                                 const int* __restrict__ jmsl, const u64* __restrict__ jfmask,
+                                                 Rec* __restrict__ segbest, int Smax, Rec* __restrict__ tilefirst) {
   constexpr int KK = 4 * NW;
   __shared__ u64 cur_score[kSegLds], best_score[kSegLds], best_key[kSegLds];
   __shared__ unsigned cur_p[kSegLds];
@@ -341,6 +345,18 @@ __global__ __launch_bounds__(kTT) void tt_search(const uint2* __restrict__ list,
     cur_p[i] = 0xffffffffu;
   }
   for (int i = tid; i <= NS; i += kTT) seg_b[i] = sg.begin[sLo + i];
+  u64* seg_fm = nullptr;  // [NS] the segments' feature masks, then their union
+  if constexpr (MASKED) {
+    __shared__ u64 fm_s[kSegLds + 1];
+    seg_fm = fm_s;
+    if (tid == 0) fm_s[NS] = 0;
+    __syncthreads();
+    for (int i = tid; i < NS; i += kTT) {
+      const u64 m = jfmask[sg.job[sLo + i]];
+      fm_s[i] = m;
+      atomicOr(&fm_s[NS], m);
+    }
+  }
   __syncthreads();
 
   // the segment of every item (the same in all features); items past the
@@ -365,6 +381,9 @@ __global__ __launch_bounds__(kTT) void tt_search(const uint2* __restrict__ list,
 
   const int f_end = min(F, (y + 1) * fc);
   for (int f = y * fc; f < f_end; ++f) {
+    if constexpr (MASKED) {
+      if (!((seg_fm[NS] >> f) & 1)) continue;  // uniform: no segment of the tile may use f
+    }
     const uint2* L = list + (size_t)f * Tp;
     uint2 e[kTI];
     load_items(L, q0, Tl, e);
@@ -467,7 +486,9 @@ __global__ __launch_bounds__(kTT) void tt_search(const uint2* __restrict__ list,
     // features come in rising order: only a strictly larger score replaces
     for (int i = tid; i < NS; i += kTT) {
       const u64 cs = cur_score[i];
-      if (cs > best_score[i]) {
+      bool take = cs > best_score[i];
+      if constexpr (MASKED) take = take && ((seg_fm[i] >> f) & 1);
+      if (take) {
         best_score[i] = cs;
         best_key[i] = ((u64)(unsigned)f << 32) | cur_p[i];
       }
@@ -816,7 +837,7 @@ struct Layout {
   int64_t T = 0, Tp = 0;
   int NT = 0, NTn = 0, Smax = 0, ny = 1, fc = 1;
   size_t list[2], flags, tilecnt, ptile, ftile, segbest, tilefirst, seg[2][5], dec, bf, bp, cl, E, jobi, rootcnt,
-      summary, total;
+      summary, fmask, total;
 };
 
 inline size_t carve(size_t& at, size_t bytes) {
@@ -870,6 +891,7 @@ bool make_layout(int64_t n, int F, int J, const vad_tree_job* jobs, Layout& L) {
   L.jobi = carve(at, (size_t)15 * J * 4);
   L.rootcnt = carve(at, (size_t)J * kKP * 4);
   L.summary = carve(at, 256);
+  L.fmask = carve(at, (size_t)J * 8);
   L.total = at;
   return true;
 }
@@ -888,8 +910,8 @@ size_t tree_train_ws_bytes(int64_t n, int F, int n_jobs, const vad_tree_job* job
   } while (0)
 
 int tree_train_run(const float* x, const uint8_t* y, int64_t n64, int F, int K, const int32_t* order,
-                   const uint8_t* mask, int J, const vad_tree_job* jobs, const vad_tree_tables& out, void* ws,
-                   size_t ws_bytes, int32_t* n_levels, hipStream_t st) {
+                   const uint8_t* mask, const uint64_t* feature_masks, int J, const vad_tree_job* jobs,
+                   const vad_tree_tables& out, void* ws, size_t ws_bytes, int32_t* n_levels, hipStream_t st) {
   Layout L;
   if (!make_layout(n64, F, J, jobs, L) || ws_bytes < L.total) return VAD_EINVAL;
   const int n = (int)n64, T = (int)L.T, Tp = (int)L.Tp;
@@ -914,6 +936,11 @@ int tree_train_run(const float* x, const uint8_t* y, int64_t n64, int F, int K, 
   int* ji = (int*)(w + L.jobi);
   TT_CHECK(hipMemcpyAsync(ji, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, st));
   TT_CHECK(hipMemsetAsync(w + L.rootcnt, 0, (size_t)J * kKP * 4, st));
+  const u64* jfmask = nullptr;
+  if (feature_masks) {
+    TT_CHECK(hipMemcpyAsync(w + L.fmask, feature_masks, (size_t)J * 8, hipMemcpyHostToDevice, st));
+    jfmask = (const u64*)(w + L.fmask);
+  }
   Jobs jb;
   jb.n = ji;
   jb.off = ji + J;
@@ -980,12 +1007,19 @@ int tree_train_run(const float* x, const uint8_t* y, int64_t n64, int F, int K, 
     const int NTl = (Tl + kTile - 1) / kTile;
     hipLaunchKernelGGL(tt_class_tiles, dim3(NTl, F), dim3(kTT), 0, st, list[cur], Tp, Tl, tilecnt, L.NT);
     hipLaunchKernelGGL(tt_carry<kKP>, dim3(F), dim3(kTT), 0, st, tilecnt, NTl, L.NT);
-    if (K <= 4)
-      hipLaunchKernelGGL(tt_search<1>, dim3(NTl, L.ny), dim3(kTT), 0, st, list[cur], Tp, Tl, F, L.fc, tilecnt, L.NT,
-                         sg[par], S, jb.msl, segbest, L.Smax, tilefirst);
+    const dim3 sgrid(NTl, L.ny);
+    if (K <= 4 && !jfmask)
+      hipLaunchKernelGGL((tt_search<1, false>), sgrid, dim3(kTT), 0, st, list[cur], Tp, Tl, F, L.fc, tilecnt, L.NT,
+                         sg[par], S, jb.msl, jfmask, segbest, L.Smax, tilefirst);
+    else if (!jfmask)
+      hipLaunchKernelGGL((tt_search<2, false>), sgrid, dim3(kTT), 0, st, list[cur], Tp, Tl, F, L.fc, tilecnt, L.NT,
+                         sg[par], S, jb.msl, jfmask, segbest, L.Smax, tilefirst);
+    else if (K <= 4)
+      hipLaunchKernelGGL((tt_search<1, true>), sgrid, dim3(kTT), 0, st, list[cur], Tp, Tl, F, L.fc, tilecnt, L.NT,
+                         sg[par], S, jb.msl, jfmask, segbest, L.Smax, tilefirst);
     else
-      hipLaunchKernelGGL(tt_search<2>, dim3(NTl, L.ny), dim3(kTT), 0, st, list[cur], Tp, Tl, F, L.fc, tilecnt, L.NT,
-                         sg[par], S, jb.msl, segbest, L.Smax, tilefirst);
+      hipLaunchKernelGGL((tt_search<2, true>), sgrid, dim3(kTT), 0, st, list[cur], Tp, Tl, F, L.fc, tilecnt, L.NT,
+                         sg[par], S, jb.msl, jfmask, segbest, L.Smax, tilefirst);
     hipLaunchKernelGGL(tt_decide, dim3((S + 3) / 4), dim3(kTT), 0, st, list[cur], Tp, sg[par], S, level, jb, tilecnt,
                        L.NT, segbest, L.Smax, tilefirst, L.ny, dec, bf, bp, cl, o);
     hipLaunchKernelGGL(tt_scan, dim3(1), dim3(kTT), 0, st, sg[par], S, jb, J, par, dec, bp, cl, E, Estride, summary,

@@ -337,6 +337,21 @@ hipError_t launch_tree_row_scores(const TreeNode* nodes, int n_nodes, const floa
 hipError_t launch_tree_window_scores(const TreeNode* nodes, const TreeNodeC* cnodes, int n_nodes,
                                      const float* node_score, const float* mfcc, int64_t n_rows, int mfcc_n, int mode,
                                      float* scores, hipStream_t st);
+// Random forest (forest_kernel.hip): tree t is the nodes [roots[t],
+// roots[t + 1]) of both tables, its root first and its child indices relative
+// to the root; proba holds K class shares per node (rows of leaves are read).
+struct ForestDev {
+  const TreeNode* nodes;
+  const TreeNodeC* cnodes;
+  const int* roots;  // T + 1 entries, the last the node count
+  const double* proba;
+  int T;
+  int K;
+};
+hipError_t launch_forest_rows(const ForestDev& f, const float* x, int64_t n, int dim, int active, uint8_t* labels,
+                              float* scores, hipStream_t st);
+hipError_t launch_forest_windows(const ForestDev& f, int max_lds_tree, const float* mfcc, int64_t n_rows, int mfcc_n,
+                                 int mode, int active, uint8_t* labels, float* scores, hipStream_t st);
 // FFN training (train_kernel.hip).  ffn_train_lds_bytes: LDS of one
 // workgroup of the step kernel (train) or of the evaluation kernel; the C
 // entries refuse what does not fit in 160 KiB before they launch.
@@ -351,9 +366,11 @@ hipError_t launch_ffn_eval(int n_layers, const int32_t* dims, const float* state
 // Decision-tree training (tree_train_kernel.hip).  The C entries have checked
 // every argument; tree_train_ws_bytes is 0 where the sizes do not fit.
 size_t tree_train_ws_bytes(int64_t n, int F, int n_jobs, const vad_tree_job* jobs);
+// feature_masks (host, one word per job; null: every feature): bit f set when
+// the job may split on feature f.
 int tree_train_run(const float* x, const uint8_t* y, int64_t n, int F, int K, const int32_t* order,
-                   const uint8_t* mask, int n_jobs, const vad_tree_job* jobs, const vad_tree_tables& out, void* ws,
-                   size_t ws_bytes, int32_t* n_levels, hipStream_t st);
+                   const uint8_t* mask, const uint64_t* feature_masks, int n_jobs, const vad_tree_job* jobs,
+                   const vad_tree_tables& out, void* ws, size_t ws_bytes, int32_t* n_levels, hipStream_t st);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel and device
 // (`done`: one bit per device ordinal, a static of the launch site).

@@ -69,6 +69,9 @@ def split_clip(n_samples, rank, world, frame_size=FRAME_SIZE, hop=HOP):
 
 def classify_clip_shard(pipe, audio_segment, shard: ClipShard, out=None, stream=None):
     """Labels of this rank's windows from its (already sliced, device) segment."""
+    from .forest import ForestClassifier
+    if isinstance(getattr(pipe, "ffn", None), ForestClassifier):
+        raise ValueError("vad_amd.dist shards the FFN and decision-tree pipelines: a forest is not sharded")
     if shard.n_windows == 0:
         return torch.empty((0,), dtype=torch.uint8, device=audio_segment.device)
     if getattr(pipe.cfg, "preemph", None) is not None and shard.sample_lo > 0:

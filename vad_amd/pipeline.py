@@ -35,12 +35,17 @@ class VadPipeline:
     def __init__(self, ffn=None, cfg: MfccConfig = MfccConfig(), mode="analyser"):
         """ffn: an FFNClassifier (or its layers), or a TreeClassifier / fitted
         sklearn DecisionTreeClassifier (the classifier vad.py deploys)."""
+        from .forest import ForestClassifier
         from .tree import TreeClassifier
         self.cfg = cfg
         self.plan = MfccPlan.from_config(cfg)
         if ffn is not None and TreeClassifier.looks_like_sklearn_tree(ffn):
             ffn = TreeClassifier.from_sklearn(ffn)
-        if ffn is not None and not isinstance(ffn, (FFNClassifier, TreeClassifier)):
+        # a ForestClassifier (or a fitted sklearn forest / bagging of trees) runs
+        # wherever the tree does on the two-kernel clip path
+        if ffn is not None and ForestClassifier.looks_like_sklearn_forest(ffn):
+            ffn = ForestClassifier.from_sklearn(ffn)
+        if ffn is not None and not isinstance(ffn, (FFNClassifier, TreeClassifier, ForestClassifier)):
             ffn = FFNClassifier(ffn)
         self.ffn = ffn
         self.mode = _lib.FEAT_ANALYSER if mode == "analyser" else _lib.FEAT_OFFLINE
@@ -130,7 +135,7 @@ class VadPipeline:
             check_out(out, (rows,), torch.uint8, audio.device, "out")
         if not isinstance(self.ffn, FFNClassifier):  # decision tree: MFCC, then windows
             if fused:
-                raise ValueError("the fused kernel runs the FFN classifiers only")
+                raise ValueError("the fused kernel runs the FFN classifiers only (no decision tree, no forest)")
             return self.ffn.window_labels(self.mfcc(audio, stream=stream), self.mode, out=out,
                                           stream=stream)
         audio = self._staged(audio, stream)

@@ -35,7 +35,11 @@ from .config import FRAMES_BUFFER_SIZE, NOISE_BUFFER_SIZE, PROCESSING_FRAME_INDE
 from .ffn import FFNClassifier
 from .mfcc import get_mel_filterbanks
 from .plan import MfccPlan, window_features
+from .forest import ForestClassifier
 from .tree import TreeClassifier
+
+_NO_FOREST = ("SKLearnAnalyzer's per-frame step walks one decision tree: a forest runs on clips "
+              "(vad_amd.pipeline.VadPipeline)")
 
 logger = logging.getLogger(__name__)
 
@@ -63,6 +67,8 @@ class SKLearnAnalyzer(Analyser):
         if str(fname).endswith(".npz"):
             with np.load(fname, allow_pickle=False) as z:
                 is_tree = "threshold" in z.files
+                if "roots" in z.files:
+                    raise ValueError(_NO_FOREST)
             self.classifier = TreeClassifier.load(fname) if is_tree else FFNClassifier.load(fname)
         else:
             # the reference unpickles its classifier file (:34-35); a fitted
@@ -72,6 +78,8 @@ class SKLearnAnalyzer(Analyser):
                 self.classifier = pickle.load(f)
             if TreeClassifier.looks_like_sklearn_tree(self.classifier):
                 self.classifier = TreeClassifier.from_sklearn(self.classifier)
+            elif ForestClassifier.looks_like_sklearn_forest(self.classifier):
+                raise ValueError(_NO_FOREST)
 
         self._plan = MfccPlan(self.filterbank, mfcc_num, fft_n)
         dev = torch.device("cuda", torch.cuda.current_device())

@@ -178,6 +178,10 @@ class StreamBatch:
             raise ValueError("input_dtype must be torch.float32 or torch.int16")
         if tree_walk not in _TREE_WALKS:
             raise ValueError("tree_walk must be 'auto' or 'global'")
+        from .forest import ForestClassifier
+        if isinstance(ffn, ForestClassifier) or ForestClassifier.looks_like_sklearn_forest(ffn):
+            raise ValueError("the hop kernels walk one decision tree: a forest runs on clips (VadPipeline), "
+                             "not in a StreamBatch")
         if not isinstance(ffn, (FFNClassifier, TreeClassifier)):
             ffn = TreeClassifier.from_sklearn(ffn) if TreeClassifier.looks_like_sklearn_tree(ffn) \
                 else FFNClassifier(ffn)

@@ -20,6 +20,12 @@ tree for smaller values of either is the big tree cut short: ``prune``.
 ``grid`` therefore trains one tree per (fold, ``min_samples_leaf``) and prunes
 for the rest: the reference's 112 x 3 fits are 12 device jobs.
 
+A job may carry a feature subset (a fifth element): the tree then splits on
+those columns only, and ``fit_forest`` trains a bagged forest that way -- rows
+sampled without replacement and a feature subset per tree, drawn on the host
+(``forest_draws``), all trees in one call; it returns a
+``vad_amd.forest.ForestClassifier``.
+
 There is no CPU path: the trees grow in the HIP kernels or the call raises.
 """
 from __future__ import annotations
@@ -172,6 +178,62 @@ def prune(tree, max_depth, min_samples_split):
                           n_node_samples=t["n_node_samples"], depth=t["depth"], value=t["value"])
 
 
+def feature_mask(features, F):
+    """The 64-bit mask of a job's ``features`` (distinct indices into 0..F-1,
+    at least one); None for None (all features)."""
+    if features is None:
+        return None
+    f = np.asarray(features.cpu() if isinstance(features, torch.Tensor) else features)
+    if f.dtype.kind not in "iu" or f.ndim != 1 or f.size < 1:
+        raise ValueError("a job's features must be a 1-D sequence of integer column indices, at least one")
+    f = f.astype(np.int64)
+    if f.min() < 0 or f.max() >= F or np.unique(f).size != f.size:
+        raise ValueError(f"a job's features must be distinct indices into 0..{F - 1}")
+    return int(sum(1 << int(i) for i in f))
+
+
+def forest_draws(n, F, n_trees, max_samples=1.0, max_features="sqrt", seed=0):
+    """The row and feature subsets ``fit_forest`` trains tree t on, as
+    [(rows_t, feats_t), ...] (None: all).  ``rng = np.random.default_rng(seed)``;
+    for t = 0 .. n_trees-1 in order
+    ``rows_t = np.sort(rng.choice(n, m, replace=False))`` with
+    m = max(1, int(max_samples * n)) for a float or the integer itself, then
+    ``feats_t = np.sort(rng.choice(F, k, replace=False))`` with k =
+    max(1, int(sqrt(F))) for "sqrt", max(1, int(max_features * F)) for a
+    float, the integer itself, F for None.  Both draws are always made; a draw
+    of everything (m == n, k == F) is then reported as None."""
+    n, F, n_trees = int(n), int(F), int(n_trees)
+    if n_trees < 1:
+        raise ValueError("n_trees must be >= 1")
+
+    def count(v, total, what):
+        if isinstance(v, (float, np.floating)):
+            if not 0.0 < v <= 1.0:
+                raise ValueError(f"{what} as a fraction must be in (0, 1], got {v}")
+            return max(1, int(v * total))
+        c = int(v)
+        if not 1 <= c <= total:
+            raise ValueError(f"{what} must be 1..{total}, got {v}")
+        return c
+
+    m = count(max_samples, n, "max_samples")
+    if max_features is None:
+        k = F
+    elif isinstance(max_features, str):
+        if max_features != "sqrt":
+            raise ValueError('max_features must be "sqrt", a fraction, a count or None')
+        k = max(1, int(np.sqrt(F)))
+    else:
+        k = count(max_features, F, "max_features")
+    rng = np.random.default_rng(seed)
+    draws = []
+    for _ in range(n_trees):
+        rows = np.sort(rng.choice(n, m, replace=False))
+        feats = np.sort(rng.choice(F, k, replace=False))
+        draws.append((None if m == n else rows, None if k == F else feats))
+    return draws
+
+
 class TreeTrainer:
     """Exact Gini trees on the device, the reference's parameters as defaults."""
 
@@ -186,16 +248,24 @@ class TreeTrainer:
 
     def fit_many(self, X, y, jobs, node_capacity=None):
         """One tree per job ``(rows, max_depth, min_samples_split,
-        min_samples_leaf)``; ``rows``: indices into X without repeats, in any
-        order, or None for all.  ``node_capacity`` (tests): nodes to provide
-        per job instead of the bound that always suffices."""
+        min_samples_leaf)`` or ``(rows, max_depth, min_samples_split,
+        min_samples_leaf, features)``; ``rows``: indices into X without
+        repeats, in any order, or None for all; ``features``: the distinct
+        columns the job may split on, or None for all (the tree is the one of
+        ``X[:, features]`` with its feature indices mapped back).
+        ``node_capacity`` (tests): nodes to provide per job instead of the
+        bound that always suffices."""
         Xc, yi, classes = check_rows(X, y)
         n, F = (int(v) for v in Xc.shape)
         K = max(2, len(classes))
         if not jobs:
             return []
-        params, row_sets = [], []
-        for rows, md, mss, msl in jobs:
+        params, row_sets, fmasks = [], [], []
+        for job in jobs:
+            if len(job) not in (4, 5):
+                raise ValueError("a job is (rows, max_depth, min_samples_split, min_samples_leaf[, features])")
+            rows, md, mss, msl = job[:4]
+            fmasks.append(feature_mask(job[4] if len(job) == 5 else None, F))
             params.append(check_params(md, mss, msl))
             if rows is not None:
                 rows = np.asarray(rows.cpu() if isinstance(rows, torch.Tensor) else rows).astype(np.int64).ravel()
@@ -234,9 +304,13 @@ class TreeTrainer:
             levels = ctypes.c_int32(0)
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
-            rc = lib().vad_tree_train(Xd.data_ptr(), yd.data_ptr(), n, F, K, order.data_ptr(),
-                                      None if mask is None else mask.data_ptr(), J, desc, ctypes.byref(tb),
-                                      ws.data_ptr(), need, ctypes.byref(levels), stream_ptr())
+            fm = None
+            if any(m is not None for m in fmasks):
+                fm = (ctypes.c_uint64 * J)(*((1 << F) - 1 if m is None else m for m in fmasks))
+            rc = lib().vad_tree_train_features(Xd.data_ptr(), yd.data_ptr(), n, F, K, order.data_ptr(),
+                                               None if mask is None else mask.data_ptr(), fm, J, desc,
+                                               ctypes.byref(tb), ws.data_ptr(), need, ctypes.byref(levels),
+                                               stream_ptr())
             self.last_call_seconds = time.perf_counter() - t0
             if rc == VAD_ENOMEM:
                 status = out["status"].cpu().numpy()
@@ -253,6 +327,20 @@ class TreeTrainer:
             trees.append(TreeClassifier(*(t[k] for k in _NODE_KEYS[:6]), classes, F, n_node_samples=t["n_node_samples"],
                                         depth=t["depth"], value=t["value"][:, :max(len(classes), 1)]))
         return trees
+
+    def fit_forest(self, X, y, n_trees, max_samples=1.0, max_features="sqrt", seed=0):
+        """A ForestClassifier of ``n_trees`` trees with the trainer's three
+        parameters, tree t on the rows and features of ``forest_draws`` (drawn
+        on the host, WITHOUT replacement), all in one ``fit_many`` call."""
+        from .forest import ForestClassifier
+        Xc, yi, classes = check_rows(X, y)
+        n, F = (int(v) for v in Xc.shape)
+        draws = forest_draws(n, F, n_trees, max_samples, max_features, seed)
+        jobs = [(r, self.max_depth, self.min_samples_split, self.min_samples_leaf, f) for r, f in draws]
+        trees = self.fit_many(Xc, yi, jobs)
+        for t in trees:  # fit_many saw class indices
+            t.classes_ = classes
+        return ForestClassifier.from_trees(trees)
 
     def grid(self, X, y, max_depth, min_samples_split, min_samples_leaf, folds):
         """Cross-validated accuracy of every (max_depth, min_samples_split,
