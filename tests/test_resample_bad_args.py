@@ -69,6 +69,40 @@ def test_plan_create_refuses(lib):
     assert lib.vad_resample_stream_state_bytes(N, 4) == 0
 
 
+def test_plan_create_at_the_lds_limits(lib):
+    """The last plan that fits and the first that does not, at either limit of
+    16,384 floats: the input tile (1023 * down + T for up = 1) and the phase
+    table (up * (T | 1))."""
+    for up, down, n_taps, delay in ((1, 15, 301, 10),         # 240 kHz: 15,345 + 301 = 15,646 floats of input tile
+                                    (640, 799, 15981, 10)):   # 19,975 Hz: T = 25, 640 * 25 = 16,000 floats of table
+        rc, h = create(lib, up, down)
+        assert rc == 0 and h.value, (up, down)
+        assert 20 * max(up, down) + 1 == n_taps and lib.vad_resample_delay(h) == delay
+        assert lib.vad_resample_plan_destroy(h) == 0
+    for up, down, n_taps in ((1, 16, 321),        # 16,368 + 321 = 16,689 floats of input tile
+                             (640, 801, 16021),   # T = 26, rows of 27: 17,280 floats of table
+                             (640, 800, 16001)):  # the shortest filter with T = 26 is of no reduced ratio
+        assert 20 * max(up, down) + 1 == n_taps
+        rc, h = create(lib, up, down)
+        assert rc == E and not h.value, (up, down)
+    # T = 26 by the tap count alone does not pass as the 640 / 799 plan either
+    rc, h = create(lib, 640, 799, n_taps=16001)
+    assert rc == E and not h.value
+
+
+@pytest.mark.parametrize("fn", STREAM)
+def test_stream_window_at_the_lds_limit(lib, fn):
+    """240 kHz: hops of 2400 samples behind 300 of history; six fit the
+    16,384-float window (14,700), seven do not (17,100)."""
+    rc, h = create(lib, 1, 15)
+    assert rc == 0
+    assert lib.vad_resample_stream_state_bytes(h, 3) == 3 * 301 * 4
+    for k, want in ((6, 0), (7, E)):  # zero streams: the arguments are checked, nothing is launched
+        assert getattr(lib, fn)(h, INP, 2400, 2400, 0, k, 160, STATE, OUT, N) == want, k
+    assert getattr(lib, fn)(h, INP, 2400, 4 * 2400, 4, 7, 160, STATE, OUT, N) == E
+    assert lib.vad_resample_plan_destroy(h) == 0
+
+
 @pytest.mark.parametrize("fn", BATCH)
 def test_batch_entries_refuse(lib, plan, fn):
     def call(**kw):

@@ -5,6 +5,7 @@ refuses what the device cannot take."""
 import numpy as np
 import pytest
 
+import resample_edge_plans as E
 from vad_amd import resample as R
 from vad_amd.config import MfccConfig
 
@@ -12,6 +13,10 @@ from vad_amd.config import MfccConfig
 RATES = [(48000, 16000), (8000, 16000), (44100, 16000), (11025, 16000), (96000, 16000), (24000, 16000),
          (16000, 16000)]
 RATIOS = [(1, 3), (2, 1), (160, 441), (640, 441), (1, 6), (2, 3), (1, 1)]
+# and every edge plan (tests/resample_edge_plans.py) not among them
+EDGE = [r for r in E.EDGE_RATES if (r, 16000) not in RATES]
+RATES += [(r, 16000) for r in EDGE]
+RATIOS += [E.EDGE_PLANS[r][:2] for r in EDGE]
 
 
 @pytest.mark.parametrize("rates,ratio", list(zip(RATES, RATIOS)))
@@ -116,6 +121,92 @@ def test_every_required_rate_fits():
     assert R.ResampleSpec(44100).phase_len == 56 and R.ResampleSpec(11025).phase_len == 21
 
 
+@pytest.mark.parametrize("rate", E.EDGE_RATES)
+def test_edge_plans_are_where_the_tests_expect_them(rate):
+    """up, down, T, table, tile span, delay and history of every edge rate: a
+    change of the filter design moves these, and the device tests with them."""
+    s = R.ResampleSpec(rate)
+    assert E.plan_sizes(s) == E.EDGE_PLANS[rate]
+    up, down, T, table, span, delay, hist = E.EDGE_PLANS[rate]
+    assert table <= R.MAX_TABLE and span <= R.MAX_SPAN
+    assert s.row_stride == T | 1 and s.row_stride % 2 == 1
+    if rate % 100 == 0:  # a stream's window: the history and K hops
+        m = R.StreamModel(1, rate)
+        assert m.hop_in == rate // 100 and m.spec.history == hist
+
+
+def test_edge_plans_reach_the_limits():
+    sizes = np.array([E.EDGE_PLANS[r] for r in E.EDGE_RATES])
+    assert sizes[:, 3].max() == 16000 and sizes[:, 4].max() == 15646  # of 16384 each
+    assert sizes[:, 2].max() == 301 and sizes[:, 6].max() == 300 and sizes[:, 6].min() == 20
+    assert {26, 28} <= set(sizes[:, 2].tolist())  # even T, rows padded by one
+    assert sorted(sizes[:, 5].tolist())[-2:] == [160, 320]  # delays of one and two whole hops
+    # the next plan past either limit is refused (test_value_errors), so these are the last that fit
+    assert 640 * (26 | 1) > R.MAX_TABLE and 1023 * 16 + 321 > R.MAX_SPAN
+
+
+@pytest.mark.parametrize("rate", E.EDGE_RATES)
+def test_the_bound_sees_an_off_by_one(rate):
+    """The device test accepts |device - model| <= gamma sum |h||x|.  A kernel
+    whose jl were one input sample off, or whose phase row r were one off,
+    must fall outside it: on more than half of the outputs of every input the
+    device test uses, white int16 noise.  Adjacent rows at 16100 and 15975
+    are 1/160 and 1/640 of a sample apart, and still every case separates."""
+    s = R.ResampleSpec(rate)
+    h32 = E.taps32(s)
+    worst = 1.0
+    for n in E.lengths(s, R.TILE_OUT):
+        x = E.clip_input(rate, n)
+        want = R.resample_model(x, s, taps=h32)
+        assert np.array_equal(E.shifted_model(x, s, h32), want)  # the unshifted form is the model
+        if n == 0:
+            continue
+        bound = E.chain_bound(x, s)
+        for kw in (dict(dj=1), dict(dj=-1), dict(dq=1), dict(dq=-1)):
+            outside = float((np.abs(E.shifted_model(x, s, h32, **kw) - want) > bound).mean())
+            worst = min(worst, outside)
+            assert outside > 0.5, (rate, n, kw, outside)
+    print(f"{rate} Hz: at least {worst:.4f} of the outputs of a model off by one lie outside the bound")
+
+
+def test_edge_sessions_script_holds_its_cases():
+    """The workload of test_gpu_resample_ratios.py's sessions tests, checked
+    here against the float64 sessions model: the cases it is there for occur."""
+    import resample_sessions_reference as SR
+    rates, K = E.SESSION_RATES, 3
+    counts, restart, rate = E.sessions_script()
+    B, S = counts.shape
+    hn = [R.ResampleSpec(r).history for r in rates]
+    assert hn == [300, 20, 20, 120, 20, 60, 20, 40] and len(rates) == R.MAX_RATES
+    assert restart[0].all() and set(counts.reshape(-1).tolist()) == set(range(-1, K + 2))
+    rows = SR.session_rows(counts, restart, rate, len(rates), K)
+    assert [s["rate"] for s in rows[0][1:]] == [0, 1, 0, 1]  # 240000 -> 500 -> 240000 -> 500
+    assert [s["rate"] for s in rows[7][1:]] == [7, 0, 7]     # clamped indices
+    shorter = sum(hn[b["rate"]] < hn[a["rate"]] and len(a["rows"]) > 0 for s in range(S)
+                  for a, b in zip(rows[s][1:], rows[s][2:]))
+    assert shorter == 7
+    stalls = [(b, s) for b in range(B) for s in range(S) if counts[b, s] <= 0 and not restart[b, s]]
+    assert len(stalls) >= 6 and (3, 1) in stalls
+    # the model runs it: every session of the model is the clip model of its hops, delayed
+    x = SR.audio(B, K, S, 2400, seed=979)
+    m = SR.SessionsResampleModel(S, rates, K)
+    emitted = []
+    for b in range(B):
+        out = m.step(x[b], counts[b], restart[b], rate[b])
+        assert np.isnan(out[:, 5]).all() == (counts[b, 5] <= 0)
+        emitted.append(min(m.model[1].emitted, m.model[1].spec.delay))
+    assert emitted[:5] == [160, 0, 160, 160, 320]  # stream 1: restarted inside the delay of 500 Hz
+    for s in range(S):
+        for sess in m.sessions[s]:
+            if not sess["hops"]:
+                continue
+            spec = R.ResampleSpec(rates[sess["rate"]])
+            whole = R.resample_model(np.concatenate(sess["hops"]), spec)
+            got = np.concatenate(sess["rows"])
+            d = min(spec.delay, len(got))
+            assert not got[:d].any() and np.array_equal(got[d:], whole[:len(got) - d]), (s, sess["rate"])
+
+
 def test_value_errors():
     import torch
     for bad in (0, -8000, 8000.5):
@@ -131,6 +222,13 @@ def test_value_errors():
         R.Resampler(16001)
     with pytest.raises(ValueError, match="LDS"):
         R.ResampleSpec(16000 * 17)     # 1 / 17: the input tile
+    with pytest.raises(ValueError, match="LDS"):
+        R.ResampleSpec(256000)         # 1 / 16: 1023 * 16 + 321 = 16,689 floats of input tile, the first too long
+    with pytest.raises(ValueError, match="LDS"):
+        R.ResampleSpec(20025)          # 640 / 801: T = 26, 640 rows of 27 floats, the first 640-row table too large
+    assert R.ResampleSpec(240000).phase_len == 301 and R.ResampleSpec(19975).phase_len == 25  # the last that fit
+    with pytest.raises(ValueError):
+        R.StreamResampler(1, 240000, hops_per_step=7)  # 7 hops of 2400 samples and 300 of history
     with pytest.raises(ValueError, match="100 Hz"):
         R.StreamResampler(2, 11025)
     with pytest.raises(ValueError):
