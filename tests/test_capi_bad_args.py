@@ -80,6 +80,12 @@ neutral = {
     "vad_format_csv_rows_null": int(L.vad_format_csv_rows(N, 3, 39, 1.0, N, 100)),
     "vad_stream_hop_block_waves_none": [int(L.vad_stream_hop_block_waves(30000, 0, 1)),
                                         int(L.vad_stream_hop_block_waves(30000, 10, 0))],
+    # the limits of vad_simple_features, with no frame so that nothing launches:
+    # L = 8193 from 8191 samples; 8192 samples and a pad; bands up to the last bin; one bin more
+    "vad_simple_features_limits": [int(L.vad_simple_features(N, 0, 8191, 8191, 8193, 1, 512, 4, N, N)),
+                                   int(L.vad_simple_features(N, 0, 8192, 8192, 8194, 1, 512, 4, N, N)),
+                                   int(L.vad_simple_features(N, 0, 400, 400, 512, 56, 128, 4, N, N)),
+                                   int(L.vad_simple_features(N, 0, 400, 400, 512, 56, 129, 4, N, N))],
 }
 print(json.dumps({"calls": res, "neutral": neutral}))
 '''
@@ -102,3 +108,5 @@ def test_every_entry_refuses_bad_arguments():
     assert n["vad_stream_ring_floats_neg"] <= 0
     assert n["vad_format_csv_rows_null"] < 0
     assert n["vad_stream_hop_block_waves_none"] == [0, 0]  # no streams or no hops: no launch, no block
+    lim = n["vad_simple_features_limits"]
+    assert lim[0] == 0 and lim[1] < 0 and lim[2] == 0 and lim[3] < 0

@@ -12,6 +12,12 @@ int16 PCM, another FFT length), spectra, window features, the FFN window
 kernel (split-f16 topologies, 3 classes, exact f32, with logits), the fused
 kernel, the decision tree, the streaming hop kernel (one hop and blocks of
 8) and the three-kernel step, and SimpleAnalyser features.
+
+Other files run the same check (the poison fixture and check() below) on
+their own kernels: tests/test_gpu_simple_stream.py and
+tests/test_gpu_simple_stream_sessions.py (the stream block kernels),
+tests/test_gpu_simple_lengths.py (SimpleAnalyser features at L = 1024, 2048,
+4096, 8192, 257 and 8193: every LDS layout of the wave and direct kernels).
 """
 import ctypes
 import os
