@@ -923,6 +923,51 @@ int vad_stream_hops_tree_sessions_i16(const vad_mfcc_plan* plan, const vad_tree_
                                       float* spec_ring, float* noise_rows, int32_t* noise_count, float* noise_est,
                                       float alpha, int32_t noise_class, int32_t update, const int32_t* hop_counts,
                                       uint8_t* restart, void* stream);
+/* Hops labelled and scored by a random forest (vad_forest above), in the hop
+ * kernel: one wave per stream, lane l walking tree l (trees 64.. in further
+ * passes), then the ordered double average of vad_features_forest -- K sums
+ * from 0, tree 0 .. T-1 in order, divided by (double)T.  labels[k *
+ * label_block_stride + s] is the first maximum (a class index), scores[k *
+ * score_block_stride + s] (when `scores` is not NULL) the fp32 share of class
+ * `active`: what vad_features_forest gives for the same MFCC rows, bit for
+ * bit.  255 / NaN during a stream's first five hops.  Frames, ring and count
+ * advance as by every other hop entry.
+ * Arguments: vad_stream_hops_tree_sessions', with the forest in place of the
+ * tree plan.  Nullable: scores; the four denoise arrays (all or none: none =
+ * no denoising, and alpha, noise_class, update are not read); hop_counts and
+ * restart (both or neither: neither = every stream takes n_hops hops).  With
+ * denoising the noise_class test uses the forest's label.
+ * `walk`: VAD_TREE_WALK_AUTO stages the compact nodes of the longest prefix of
+ * whole trees that fits in LDS beside the hop tables and one wave's scratch
+ * (vad_stream_forest_lds_trees of them) and walks the other trees from the
+ * global table; VAD_TREE_WALK_GLOBAL stages none.  Same labels and scores.
+ * Refusals (VAD_EINVAL, before any device call): a null plan, forest, frames,
+ * hop, ring, count or labels; forest n_features > 3 * mfcc_n; active outside
+ * 0 .. n_classes-1 (with or without scores); any other `walk`; the strides and
+ * overlap rules of the tree entries; a partly set denoise state, alpha outside
+ * [0, 1), update other than 0 / 1, noise_class outside 0 .. n_classes-1;
+ * hop_counts without restart or the reverse.
+ *   vad_stream_hop_forest_table_bytes  the bytes a launch stages per block
+ *                                      (for vad_stream_hop_block_waves);
+ *   vad_stream_forest_lds_trees        the leading trees an AUTO launch stages;
+ * both VAD_EINVAL for a null or table-less plan or a null forest. */
+int vad_stream_hops_forest(const vad_mfcc_plan* plan, const vad_forest* forest, float* frames, int64_t frame_stride,
+                           int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len,
+                           int64_t n_streams, int32_t n_hops, int64_t hop_block_stride, float* ring, int32_t* count,
+                           uint8_t* labels, int64_t label_block_stride, int32_t walk, int32_t active, float* scores,
+                           int64_t score_block_stride, float* spec_ring, float* noise_rows, int32_t* noise_count,
+                           float* noise_est, float alpha, int32_t noise_class, int32_t update,
+                           const int32_t* hop_counts, uint8_t* restart, void* stream);
+int vad_stream_hops_forest_i16(const vad_mfcc_plan* plan, const vad_forest* forest, float* frames,
+                               int64_t frame_stride, int32_t frame_len, const int16_t* hop, int64_t hop_stride,
+                               int32_t hop_len, int64_t n_streams, int32_t n_hops, int64_t hop_block_stride,
+                               float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride,
+                               int32_t walk, int32_t active, float* scores, int64_t score_block_stride,
+                               float* spec_ring, float* noise_rows, int32_t* noise_count, float* noise_est,
+                               float alpha, int32_t noise_class, int32_t update, const int32_t* hop_counts,
+                               uint8_t* restart, void* stream);
+int64_t vad_stream_hop_forest_table_bytes(const vad_mfcc_plan* plan, const vad_forest* forest, int32_t walk);
+int32_t vad_stream_forest_lds_trees(const vad_mfcc_plan* plan, const vad_forest* forest);
 /* Replay a captured hipGraph (hipGraphExec_t) on `stream`: the per-hop step
  * of a StreamBatch captured with its host I/O (the H2D copy of every
  * stream's new samples from pinned memory, the hop kernel, the D2H copy of

@@ -25,6 +25,9 @@ def __getattr__(name):
     if name == "ForestClassifier":
         from .forest import ForestClassifier
         return ForestClassifier
+    if name == "ForestStreamBatch":
+        from .stream import ForestStreamBatch
+        return ForestStreamBatch
     # the resamplers load the built library on first use
     if name in ("Resampler", "StreamResampler", "SessionStreamResampler", "resample_clips", "resample_model",
                 "ResampleSpec"):

@@ -158,6 +158,12 @@ SIGNATURES = {
                                                      c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp,
                                                      c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp])
        for t in ("", "_i16")},
+    **{"vad_stream_hops_forest" + t: (c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i32,
+                                              c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp,
+                                              c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp])
+       for t in ("", "_i16")},
+    "vad_stream_hop_forest_table_bytes": (c_i64, [c_vp, c_vp, c_i32]),
+    "vad_stream_forest_lds_trees": (c_i32, [c_vp, c_vp]),
     **{"vad_stream_noise_load" + t: (c_int, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_f32,
                                              c_vp])
        for t in ("", "_i16")},

@@ -21,7 +21,7 @@ SOURCES = ["capi.hip", "mfcc_kernel.hip", "ffn_kernel.hip", "tree_kernel.hip",
            "spec_generic.hip", "segments_kernel.hip", "stream_segments_kernel.hip", "train_kernel.hip",
            "tree_train_kernel.hip", "stream_tree_kernel.hip", "csv_parse_kernel.hip", "batch_kernel.hip",
            "batch_segments_kernel.hip", "simple_stream_kernel.hip", "resample_kernel.hip", "score_kernel.hip",
-           "forest_kernel.hip"]
+           "forest_kernel.hip", "stream_forest_kernel.hip"]
 # per-translation-unit code-generation flags: the FFT's packed-fp32 chains
 # run ~5% faster under the ILP-oriented machine scheduler (fewer dependent
 # pairs back to back, i.e. fewer hazard s_nops and stalls)
@@ -48,6 +48,7 @@ UNIT_FLAGS = {
     "resample_kernel.hip": [],
     "score_kernel.hip": [],
     "forest_kernel.hip": [],
+    "stream_forest_kernel.hip": [],
 }
 
 

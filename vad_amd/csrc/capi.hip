@@ -801,6 +801,8 @@ struct vad_forest {
   int n_classes;
   int n_features;
   int max_lds_tree;  // nodes of the largest tree the window kernel stages in LDS
+  int max_tree;      // nodes of the largest tree
+  int* roots_host;   // n_trees + 1: the hop kernels' staging rule reads it (stream_forest_lds_trees)
 };
 
 int vad_forest_create(int32_t n_nodes, const int32_t* feature, const double* threshold, const int32_t* left,
@@ -817,9 +819,10 @@ int vad_forest_create(int32_t n_nodes, const int32_t* feature, const double* thr
   r.push_back(n_nodes);
   std::vector<TreeNode> h((size_t)n_nodes);
   std::vector<TreeNodeC> c((size_t)n_nodes);
-  int max_lds_tree = 0;
+  int max_lds_tree = 0, max_tree = 0;
   for (int t = 0; t < n_trees; ++t) {
     const int lo = r[t], hi = r[t + 1];
+    if (hi - lo > max_tree) max_tree = hi - lo;
     if (hi - lo <= 3072 && hi - lo > max_lds_tree) max_lds_tree = hi - lo;  // kLdsNodes of the tree kernels
     for (int i = lo; i < hi; ++i) {
       TreeNode& nd = h[i];
@@ -849,6 +852,12 @@ int vad_forest_create(int32_t n_nodes, const int32_t* feature, const double* thr
   vad_forest* p = (vad_forest*)calloc(1, sizeof(vad_forest));
   if (!p) return VAD_ENOMEM;
   const size_t pb = (size_t)n_nodes * (size_t)n_classes * sizeof(double);
+  p->roots_host = (int*)malloc(r.size() * sizeof(int));
+  if (!p->roots_host) {
+    free(p);
+    return VAD_ENOMEM;
+  }
+  memcpy(p->roots_host, r.data(), r.size() * sizeof(int));
   hipError_t e = hipMalloc((void**)&p->nodes_dev, h.size() * sizeof(TreeNode));
   if (e == hipSuccess) e = hipMalloc((void**)&p->cnodes_dev, c.size() * sizeof(TreeNodeC));
   if (e == hipSuccess) e = hipMalloc((void**)&p->roots_dev, r.size() * sizeof(int));
@@ -866,6 +875,7 @@ int vad_forest_create(int32_t n_nodes, const int32_t* feature, const double* thr
   p->n_classes = n_classes;
   p->n_features = n_features;
   p->max_lds_tree = max_lds_tree;
+  p->max_tree = max_tree;
   *out = p;
   return VAD_OK;
 }
@@ -876,6 +886,7 @@ int vad_forest_destroy(vad_forest* p) {
   if (p->cnodes_dev) (void)hipFree(p->cnodes_dev);
   if (p->roots_dev) (void)hipFree(p->roots_dev);
   if (p->proba_dev) (void)hipFree(p->proba_dev);
+  free(p->roots_host);
   free(p);
   return VAD_OK;
 }
@@ -1803,6 +1814,94 @@ int vad_stream_hops_tree_sessions_i16(const vad_mfcc_plan* plan, const vad_tree_
                                    n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk,
                                    active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
                                    alpha, noise_class, update, stream, true, hop_counts, restart);
+}
+
+// ---------------------------------------------------------------------------
+// The hop kernels with a random forest (stream_forest_kernel.hip): the tree
+// sessions entry's arguments with the forest in place of the tree plan.
+// scores, the four denoise arrays (all or none) and hop_counts / restart (both
+// or neither) may be null; which are set selects the kernel.
+// ---------------------------------------------------------------------------
+static HopForest hop_forest(const vad_mfcc_plan* plan, const vad_forest* f, int32_t walk, int32_t active) {
+  const int lds_trees =
+      stream_forest_lds_trees(plan->hop_blob_n, f->roots_host, f->n_trees, walk == VAD_TREE_WALK_GLOBAL);
+  return HopForest{forest_dev(f), lds_trees, f->roots_host[lds_trees], f->max_tree, active};
+}
+
+int64_t vad_stream_hop_forest_table_bytes(const vad_mfcc_plan* plan, const vad_forest* forest, int32_t walk) {
+  if (!plan || !forest || !plan->hop_blob || plan->hop_blob_n <= 0) return VAD_EINVAL;
+  if (walk != VAD_TREE_WALK_AUTO && walk != VAD_TREE_WALK_GLOBAL) return VAD_EINVAL;
+  return (int64_t)stream_hop_forest_table_bytes(plan->hop_blob_n, hop_forest(plan, forest, walk, 0).lds_nodes);
+}
+
+int32_t vad_stream_forest_lds_trees(const vad_mfcc_plan* plan, const vad_forest* forest) {
+  if (!plan || !forest || !plan->hop_blob || plan->hop_blob_n <= 0) return VAD_EINVAL;
+  return hop_forest(plan, forest, VAD_TREE_WALK_AUTO, 0).lds_trees;
+}
+
+static int stream_hops_forest_entry(const vad_mfcc_plan* plan, const vad_forest* forest, float* frames,
+                                    int64_t frame_stride, int32_t frame_len, const void* hop, int hop_bytes,
+                                    int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,
+                                    int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels,
+                                    int64_t label_block_stride, int32_t walk, int32_t active, float* scores,
+                                    int64_t score_block_stride, float* spec_ring, float* noise_rows,
+                                    int32_t* noise_count, float* noise_est, float alpha, int32_t noise_class,
+                                    int32_t update, const int32_t* hop_counts, uint8_t* restart, void* stream) {
+  if (!plan || !forest || n_streams < 0 || n_hops < 0 || frame_len <= 0 || frame_len > 1024 || hop_len <= 0 ||
+      hop_len > frame_len || frame_stride < frame_len || hop_stride < hop_len)
+    return VAD_EINVAL;
+  if (walk != VAD_TREE_WALK_AUTO && walk != VAD_TREE_WALK_GLOBAL) return VAD_EINVAL;
+  if (n_hops > 1 && label_block_stride < n_streams) return VAD_EINVAL;
+  if (scores && n_hops > 1 && score_block_stride < n_streams) return VAD_EINVAL;
+  if (n_hops > 1 && !vad_hop_layout_disjoint(n_streams, n_hops, hop_block_stride, hop_stride, hop_len))
+    return VAD_EINVAL;
+  const bool denoise = spec_ring || noise_rows || noise_count || noise_est;  // a partly set state is refused
+  if (denoise) {
+    if (!denoise_alpha_ok(alpha) || (update != 0 && update != 1) || noise_class < 0) return VAD_EINVAL;
+    if (!denoise_state_ok(n_streams, true, spec_ring, noise_rows, noise_count, noise_est)) return VAD_EINVAL;
+  }
+  if ((hop_counts != nullptr) != (restart != nullptr)) return VAD_EINVAL;
+  // the score is the average's class `active`, computed with or without `scores`
+  if (active < 0) return VAD_EINVAL;
+  // from here on the plan and the forest are read
+  if (active >= forest->n_classes || (denoise && noise_class >= forest->n_classes)) return VAD_EINVAL;
+  if (forest->n_features > 3 * plan->host.mfcc_n) return VAD_EINVAL;
+  if (n_streams == 0 || n_hops == 0) return VAD_OK;
+  if (!frames || !hop || !ring || !count || !labels) return VAD_EINVAL;
+  if (plan->generic()) return VAD_EUNSUPPORTED;  // its FFT is the 256-point Stockham of fft_n = 512
+  if (plan->spec == kSpecWindow) return VAD_EUNSUPPORTED;  // its table blob carries no analysis window
+  const HopDenoise dn = {spec_ring, noise_rows, noise_count, noise_est, alpha, noise_class, update};
+  return (int)launch_stream_hop_forest(plan->hop_blob, plan->hop_blob_n, plan->host.n_filters, plan->n_taps,
+                                       hop_forest(plan, forest, walk, active), frames, frame_stride, frame_len, hop,
+                                       hop_bytes, hop_stride, hop_len, n_streams, plan->host.mfcc_n, ring, count,
+                                       labels, n_hops, hop_block_stride, label_block_stride, scores,
+                                       score_block_stride, denoise ? &dn : nullptr, hop_counts, restart,
+                                       (hipStream_t)stream);
+}
+
+int vad_stream_hops_forest(const vad_mfcc_plan* plan, const vad_forest* forest, float* frames, int64_t frame_stride,
+    int32_t frame_len, const float* hop, int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,
+    int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride, int32_t walk,
+    int32_t active, float* scores, int64_t score_block_stride, float* spec_ring, float* noise_rows,
+    int32_t* noise_count, float* noise_est, float alpha, int32_t noise_class, int32_t update,
+    const int32_t* hop_counts, uint8_t* restart, void* stream) {
+  return stream_hops_forest_entry(plan, forest, frames, frame_stride, frame_len, hop, 4, hop_stride, hop_len,
+                                  n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk,
+                                  active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
+                                  alpha, noise_class, update, hop_counts, restart, stream);
+}
+
+int vad_stream_hops_forest_i16(const vad_mfcc_plan* plan, const vad_forest* forest, float* frames,
+    int64_t frame_stride,
+    int32_t frame_len, const int16_t* hop, int64_t hop_stride, int32_t hop_len, int64_t n_streams, int32_t n_hops,
+    int64_t hop_block_stride, float* ring, int32_t* count, uint8_t* labels, int64_t label_block_stride, int32_t walk,
+    int32_t active, float* scores, int64_t score_block_stride, float* spec_ring, float* noise_rows,
+    int32_t* noise_count, float* noise_est, float alpha, int32_t noise_class, int32_t update,
+    const int32_t* hop_counts, uint8_t* restart, void* stream) {
+  return stream_hops_forest_entry(plan, forest, frames, frame_stride, frame_len, hop, 2, hop_stride, hop_len,
+                                  n_streams, n_hops, hop_block_stride, ring, count, labels, label_block_stride, walk,
+                                  active, scores, score_block_stride, spec_ring, noise_rows, noise_count, noise_est,
+                                  alpha, noise_class, update, hop_counts, restart, stream);
 }
 
 // n frames per stream, (S, n, frame_len) with the strides given in elements,

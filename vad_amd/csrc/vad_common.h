@@ -352,6 +352,28 @@ hipError_t launch_forest_rows(const ForestDev& f, const float* x, int64_t n, int
                               float* scores, hipStream_t st);
 hipError_t launch_forest_windows(const ForestDev& f, int max_lds_tree, const float* mfcc, int64_t n_rows, int mfcc_n,
                                  int mode, int active, uint8_t* labels, float* scores, hipStream_t st);
+// The hop kernels with a forest (stream_forest_kernel.hip): the forest and
+// what a launch does with it.  The leading lds_trees trees -- lds_nodes =
+// roots[lds_trees] compact nodes -- are staged behind the blob and walked from
+// LDS, the others from the global table.
+struct HopForest {
+  ForestDev f;
+  int lds_trees;
+  int lds_nodes;
+  int max_tree;  // the node count of the largest tree: the bound of a walk
+  int active;    // the class whose share is the score
+};
+// stream_forest_lds_trees: roots is the HOST copy (T + 1 entries).
+int stream_forest_lds_trees(int blob_n, const int* roots, int n_trees, bool force_global);
+size_t stream_hop_forest_table_bytes(int blob_n, int lds_nodes);
+// scores null: labels only; dn null: no denoising; hop_counts and restart
+// both null: no sessions
+hipError_t launch_stream_hop_forest(const float* blob, int blob_n, int nf, int n_taps, const HopForest& fr,
+                                    float* frames, int64_t fstride, int len, const void* hop, int hop_bytes,
+                                    int64_t hstride, int hlen, int64_t n_streams, int mfcc_n, float* ring, int* count,
+                                    uint8_t* labels, int n_hops, int64_t hop_kstride, int64_t lab_kstride,
+                                    float* scores, int64_t score_kstride, const HopDenoise* dn, const int* hop_counts,
+                                    uint8_t* restart, hipStream_t st);
 // FFN training (train_kernel.hip).  ffn_train_lds_bytes: LDS of one
 // workgroup of the step kernel (train) or of the evaluation kernel; the C
 // entries refuse what does not fit in 160 KiB before they launch.

@@ -167,6 +167,7 @@ class StreamBatch:
     tree_walk="auto" walks the node table from LDS when it fits
     (vad_stream_tree_max_lds_nodes) and from global memory otherwise;
     "global" always walks from global memory (same labels)."""
+    _FOREST = False  # ForestStreamBatch: the classifier is a forest
 
     def __init__(self, n_streams, ffn, cfg: MfccConfig = MfccConfig(), device=None, kernel="hop",
                  hops_per_step=1, input_dtype=torch.float32, tree_walk="auto", scores=False, active=1,
@@ -179,10 +180,26 @@ class StreamBatch:
         if tree_walk not in _TREE_WALKS:
             raise ValueError("tree_walk must be 'auto' or 'global'")
         from .forest import ForestClassifier
+        self.is_forest = False
         if isinstance(ffn, ForestClassifier) or ForestClassifier.looks_like_sklearn_forest(ffn):
-            raise ValueError("the hop kernels walk one decision tree: a forest runs on clips (VadPipeline), "
-                             "not in a StreamBatch")
-        if not isinstance(ffn, (FFNClassifier, TreeClassifier)):
+            if not self._FOREST:
+                raise ValueError("StreamBatch's hop kernels walk one decision tree: a forest in the stream is a "
+                                 "ForestStreamBatch (on clips: VadPipeline)")
+            if not isinstance(ffn, ForestClassifier):
+                ffn = ForestClassifier.from_sklearn(ffn)
+            self.is_forest = True
+            if kernel == "three":
+                raise ValueError("a forest lives in the one-kernel hop: kernel='three' has none")
+            if ffn.n_features > 3 * cfg.n_mfcc:
+                raise ValueError(f"the forest reads {ffn.n_features} features; a window has 3 * n_mfcc = "
+                                 f"{3 * cfg.n_mfcc}")
+            if not 0 <= int(active) < len(ffn.classes_):  # the kernel averages class `active` with or without scores
+                raise ValueError(f"active must be a class index below {len(ffn.classes_)}, got {active}")
+            if denoise and not 0 <= int(noise_class) < len(ffn.classes_):
+                raise ValueError(f"noise_class must be a class index below {len(ffn.classes_)}, got {noise_class}")
+        elif self._FOREST:
+            raise TypeError("ForestStreamBatch takes a ForestClassifier or a fitted sklearn forest or bagging")
+        if not isinstance(ffn, (FFNClassifier, TreeClassifier, ForestClassifier)):
             ffn = TreeClassifier.from_sklearn(ffn) if TreeClassifier.looks_like_sklearn_tree(ffn) \
                 else FFNClassifier(ffn)
         self.is_tree = isinstance(ffn, TreeClassifier)
@@ -200,7 +217,8 @@ class StreamBatch:
         if self.scores:
             if kernel == "three":
                 raise ValueError("scores come from the one-kernel hop: kernel='three' has none")
-            n_cls = ffn.score_classes() if self.is_tree else int(ffn.layers[-1][1].shape[0])
+            n_cls = len(ffn.classes_) if self.is_forest else ffn.score_classes() if self.is_tree \
+                else int(ffn.layers[-1][1].shape[0])
             if not 0 <= self.active < n_cls:
                 raise ValueError(f"active must be a class index below {n_cls}, got {active}")
         self.denoise = bool(denoise)
@@ -212,7 +230,8 @@ class StreamBatch:
             self.alpha, self.noise_class, self.noise_update = float(alpha), int(noise_class), bool(noise_update)
             if not 0.0 <= self.alpha < 1.0:  # false for NaN
                 raise ValueError(f"alpha must be in [0, 1), got {alpha}")
-            n_cls = 1 + max(int(c) for c, f in zip(ffn.leaf, ffn.feature) if f < 0) if self.is_tree \
+            n_cls = len(ffn.classes_) if self.is_forest \
+                else 1 + max(int(c) for c, f in zip(ffn.leaf, ffn.feature) if f < 0) if self.is_tree \
                 else int(ffn.layers[-1][1].shape[0])  # the tree's classes: those of its leaves
             if not 0 <= self.noise_class < n_cls:
                 raise ValueError(f"noise_class must be a class index below {n_cls}, got {noise_class}")
@@ -288,7 +307,10 @@ class StreamBatch:
         if self.kernel != "hop":
             raise ValueError("block_waves is the one-kernel hop's launch shape: kernel='three' has none")
         lib = _lib.lib()
-        if self.is_tree:
+        if self.is_forest:
+            nbytes = lib.vad_stream_hop_forest_table_bytes(self.plan.handle, self.ffn.plan.handle,
+                                                           _TREE_WALKS[self.tree_walk])
+        elif self.is_tree:
             nbytes = lib.vad_stream_hop_tree_table_bytes(self.plan.handle, self.ffn.plan.handle,
                                                          _TREE_WALKS[self.tree_walk])
         else:
@@ -365,6 +387,20 @@ class StreamBatch:
         address and strides change).  stream: a hipStream_t pointer, default
         the current stream.  sess: a sessions batch's (hop_counts, restart)
         pointers, default the batch's own tensors."""
+        if getattr(self, "_hop_head", None) is None and self.is_forest:
+            # one entry for every form: a null `scores`, denoise state or session pair switches that part off
+            L = self.cfg.frame_size
+            self._hop_name = "vad_stream_hops_forest" + ("_i16" if self._i16 else "")
+            self._hop_scores = (self.active, _lib.ptr(self.score_block) if self.scores else None, self.n) + (
+                (_lib.ptr(self._spec), _lib.ptr(self._noise), _lib.ptr(self.noise_count), _lib.ptr(self._est),
+                 self.alpha, self.noise_class, int(self.noise_update)) if self.denoise
+                else (None, None, None, None, 0.0, 0, 0))
+            self._hop_sess = (_lib.ptr(self.hop_counts), _lib.ptr(self.restart)) if self.sessions else (None, None)
+            self._hop_fn = getattr(_lib.lib(), self._hop_name)
+            self._hop_head = (self.plan.handle, self.ffn.plan.handle, _lib.ptr(self.frames), L, L)
+            self._hop_mid = (_lib.ptr(self.ring), _lib.ptr(self.count))
+            self._hop_walk = (_TREE_WALKS[self.tree_walk],)
+            self._hop_labels = {}
         if getattr(self, "_hop_head", None) is None:
             L = self.cfg.frame_size
             self._hop_name = ("vad_stream_hops_tree" if self.is_tree else "vad_stream_hops") + \
@@ -633,6 +669,38 @@ class StreamBatch:
         if fin is not None:
             fin()  # the plan before the graph it points into
         self._graph_plan = None
+
+
+class ForestStreamBatch(StreamBatch):
+    """S analyser streams labelled and scored by a random forest: a
+    ForestClassifier, or a fitted sklearn RandomForestClassifier,
+    ExtraTreesClassifier or BaggingClassifier over decision trees
+    (ForestClassifier.from_sklearn).  StreamBatch's arguments and methods, all
+    through the one-kernel hop (vad_stream_hops_forest and its _i16 form; one
+    wave per stream, lane l walking tree l): step, step_block in either
+    layout, int16 input, capture, step_host, host_pipeline, segmenter
+    (sessions=True and on= / off= / pad= included), resampler, scores=True with
+    active=, denoise=True with noise_class below len(classes_), load_noise,
+    sessions=True, tree_walk, block_waves.  kernel="three" raises ValueError.
+
+    ``label_block`` holds indices into ``classes_`` (255 during a stream's
+    first five hops); ``score_block`` holds float32(predict_proba[:, active]):
+    what ForestClassifier.window_labels / window_scores give for the stream's
+    MFCC rows, and so sklearn's predict_proba of those windows, bit for bit.
+    tree_walk="auto" walks the first ``lds_trees`` trees from LDS and the rest
+    from global memory; "global" walks every tree from global memory (same
+    labels and scores)."""
+    _FOREST = True
+
+    @property
+    def lds_trees(self):
+        """The leading trees a launch stages in LDS (vad_stream_forest_lds_trees); 0 with tree_walk="global"."""
+        if self.tree_walk == "global":
+            return 0
+        n = _lib.lib().vad_stream_forest_lds_trees(self.plan.handle, self.ffn.plan.handle)
+        if n < 0:
+            _lib.check(int(n), "vad_stream_forest_lds_trees")
+        return int(n)
 
 
 class HostPipeline:
