@@ -325,6 +325,8 @@ int vad_features_tree(const vad_tree_plan* tree, const float* mfcc, int64_t n_fr
 #define VAD_TREE_TRAIN_ROW_BITS 27
 #define VAD_TREE_TRAIN_OVERFLOW 1 /* status: node_capacity too small */
 #define VAD_TREE_TRAIN_BAD_ROWS 2 /* status: mask / n_rows / label mismatch */
+#define VAD_TREE_TRAIN_BAD_WEIGHT 4 /* status: a job's total weight above VAD_TREE_TRAIN_MAX_WEIGHT */
+#define VAD_TREE_TRAIN_MAX_WEIGHT (1 << 26) /* vad_tree_train_weighted: largest total weight of a job */
 
 typedef struct vad_tree_job {
   int64_t n_rows;
@@ -370,6 +372,31 @@ int vad_tree_train(const float* x, const uint8_t* y, int64_t n_rows, int32_t n_f
 int vad_tree_train_features(const float* x, const uint8_t* y, int64_t n_rows, int32_t n_features, int32_t n_classes,
                             const int32_t* order, const uint8_t* mask, const uint64_t* feature_masks, int32_t n_jobs,
                             const vad_tree_job* jobs, const vad_tree_tables* tables, void* workspace,
+                            size_t workspace_bytes, int32_t* n_levels, void* stream);
+/* vad_tree_train_features with an integer weight per (job, row) in the mask's
+ * place: weights[j*n_rows + r] (uint8, device) is 0 for a row that is not in
+ * job j and otherwise the weight sklearn's fit(X, y, sample_weight=) gives the
+ * row -- bootstrap counts, integer class weights or their product.  NULL: all
+ * ones (every job takes every row once, the unweighted rule and kernels).
+ * jobs[j].n_rows is the number of rows with weight > 0.  Distinct rows go on
+ * counting for n_node_samples, max_depth, min_samples_split, min_samples_leaf,
+ * a candidate's position and nan_left; the class counts are weighted: the
+ * score is (sum_k cL[k]^2) / WL + (sum_k cR[k]^2) / WR with c[k] the summed
+ * weights of class k and W their total, a node is pure when its largest count
+ * is its total, leaf is the first maximum of the weighted counts and value
+ * holds them.  A job's total weight is at most VAD_TREE_TRAIN_MAX_WEIGHT
+ * (2^26: every sum of squares is then exact in a double, as sklearn adds
+ * them).  vad_tree_train_node_capacity is unchanged (it bounds by distinct
+ * rows); the workspace is vad_tree_train_weighted_workspace_bytes.
+ * VAD_EINVAL before any HIP call: what vad_tree_train_features refuses, NULL
+ * weights with a job whose n_rows is not n_rows.  VAD_EINVAL after the
+ * launch: a job's weights do not hold jobs[j].n_rows rows above 0, a label >=
+ * n_classes, or a total weight above the limit (status says which). */
+size_t vad_tree_train_weighted_workspace_bytes(int64_t n_rows, int32_t n_features, int32_t n_classes,
+                                               int32_t n_jobs, const vad_tree_job* jobs);
+int vad_tree_train_weighted(const float* x, const uint8_t* y, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                            const int32_t* order, const uint8_t* weights, const uint64_t* feature_masks,
+                            int32_t n_jobs, const vad_tree_job* jobs, const vad_tree_tables* tables, void* workspace,
                             size_t workspace_bytes, int32_t* n_levels, void* stream);
 
 /* ---------------------------------------------------------------------------

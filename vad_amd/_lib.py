@@ -192,6 +192,9 @@ SIGNATURES = {
     "vad_scores_from_logits": (c_int, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
     "vad_tree_train_features": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                         c_sz, c_vp, c_vp]),
+    "vad_tree_train_weighted_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32, c_i32, c_vp]),
+    "vad_tree_train_weighted": (c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                        c_sz, c_vp, c_vp]),
     "vad_forest_create": (c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp]),
     "vad_forest_destroy": (c_int, [c_vp]),
     "vad_forest_predict": (c_int, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),

@@ -1294,6 +1294,42 @@ int vad_tree_train_features(const float* x, const uint8_t* y, int64_t n_rows, in
                         workspace_bytes, n_levels, (hipStream_t)stream);
 }
 
+size_t vad_tree_train_weighted_workspace_bytes(int64_t n_rows, int32_t n_features, int32_t n_classes, int32_t n_jobs,
+                                               const vad_tree_job* jobs) {
+  if (!tree_train_shape_ok(n_rows, n_features, n_classes, n_jobs, jobs)) return 0;
+  return tree_train_ws_bytes(n_rows, n_features, n_jobs, jobs, true);
+}
+
+int vad_tree_train_weighted(const float* x, const uint8_t* y, int64_t n_rows, int32_t n_features, int32_t n_classes,
+                            const int32_t* order, const uint8_t* weights, const uint64_t* feature_masks,
+                            int32_t n_jobs, const vad_tree_job* jobs, const vad_tree_tables* tables, void* workspace,
+                            size_t workspace_bytes, int32_t* n_levels, void* stream) {
+  if (!tree_train_shape_ok(n_rows, n_features, n_classes, n_jobs, jobs)) return VAD_EINVAL;  // (n_rows of 0 included)
+  if (feature_masks) {
+    const uint64_t all = n_features == 64 ? ~0ull : (1ull << n_features) - 1;
+    for (int j = 0; j < n_jobs; ++j)
+      if (!(feature_masks[j] & all)) return VAD_EINVAL;
+  }
+  if (!x || !y || !order || !tables || !workspace) return VAD_EINVAL;
+  const vad_tree_tables& t = *tables;
+  if (!t.feature || !t.threshold || !t.left || !t.right || !t.leaf || !t.nan_left || !t.n_node_samples || !t.depth ||
+      !t.value || !t.n_nodes || !t.status)
+    return VAD_EINVAL;
+  if (((uintptr_t)workspace & 255) || ((uintptr_t)t.threshold & 7)) return VAD_EINVAL;
+  if (!weights)  // all ones: every job takes every row, which the host can see
+    for (int j = 0; j < n_jobs; ++j)
+      if (jobs[j].n_rows != n_rows) return VAD_EINVAL;
+  // a row weighs at most 255: a job of more rows than this cannot stay within the limit
+  for (int j = 0; weights && j < n_jobs; ++j)
+    if (jobs[j].n_rows > VAD_TREE_TRAIN_MAX_WEIGHT) return VAD_EINVAL;
+  const size_t need = tree_train_ws_bytes(n_rows, n_features, n_jobs, jobs, true);
+  if (need == 0) return VAD_EUNSUPPORTED;
+  if (workspace_bytes < need) return VAD_EINVAL;
+  // weights of all ones are the unweighted rule: the unweighted kernels run
+  return tree_train_run(x, y, n_rows, n_features, n_classes, order, weights, feature_masks, n_jobs, jobs, t, workspace,
+                        workspace_bytes, n_levels, (hipStream_t)stream, weights != nullptr);
+}
+
 size_t vad_mfcc_ffn_workspace_bytes(const vad_mfcc_plan* plan, const vad_ffn_plan* ffn, int64_t n_samples,
                                     int32_t frame_size, int32_t hop) {
   if (!plan || !ffn) return 0;

@@ -44,6 +44,17 @@
 //
 // Nodes are numbered in level order per job here (children adjacent);
 // vad_amd/tree_train.py renumbers to sklearn's preorder on the host.
+//
+// Weighted builds (vad_tree_train_weighted; DESIGN.md section 4, "Integer row
+// weights"): a uint8 weight per (job, row) takes the mask's place (weight 0:
+// the row is not in the job).  Positions, n_node_samples and the three
+// parameters go on counting distinct rows; the class counts, the divisors of
+// the score and purity are weighted.  The 8-byte entries have no room for the
+// weight, so the kernels that count gather weights[job * n + row], the job
+// from the entry's segment.  A tile can hold 2048 * 255 of weight, so the
+// packed counters of these builds are 32-bit fields, two per 64-bit word (WW
+// words: 1, 2 or 4 for up to 2, 4 or 8 classes).  The unweighted kernels are
+// the WW = 0 / WT = false instantiations and compile to what they were.
 #include "vad_common.h"
 
 #include <vector>
@@ -163,7 +174,21 @@ __device__ __forceinline__ bool child_live(int depth, int n, unsigned maxc, int 
   return depth < md && n >= mss && n >= 2 * msl && (int)maxc < n;
 }
 
+// weighted: n counts distinct rows, W is the node's total weight
+__device__ __forceinline__ bool child_live_w(int depth, int n, unsigned maxc, unsigned W, int md, int mss, int msl) {
+  return depth < md && n >= mss && n >= 2 * msl && maxc < W;
+}
+
+// weighted class counters: 32-bit fields, two per word
+template <int WW>
+__device__ __forceinline__ void add_weight(u64 (&pk)[WW], unsigned lab, unsigned w) {
+  const u64 v = (u64)w << (32 * (lab & 1));
+#pragma unroll
+  for (int i = 0; i < WW; ++i) pk[i] += (lab >> 1) == (unsigned)i ? v : 0ull;
+}
+
 // ---- set-up: the lists from the order of all rows and the jobs' masks --------
+// (a job's weights serve as its mask: weight > 0)
 template <bool APPLY>
 __global__ __launch_bounds__(kTT) void tt_filter(const int32_t* __restrict__ order, const uint8_t* __restrict__ mask,
                                                  const float* __restrict__ x, const uint8_t* __restrict__ y, int n,
@@ -237,6 +262,33 @@ __global__ __launch_bounds__(kTT) void tt_root_counts(const uint8_t* __restrict_
   if (threadIdx.x < kKP && c[threadIdx.x]) atomicAdd(&rootcnt[j * kKP + threadIdx.x], c[threadIdx.x]);
 }
 
+// weighted roots: class counts add the weights; rows[j] counts the rows with
+// weight > 0 and wtot[j] their weight in 64 bits (the 32-bit class counts may
+// wrap when the total is past the limit: tt_init refuses the job by wtot)
+__global__ __launch_bounds__(kTT) void tt_root_counts_w(const uint8_t* __restrict__ wts, const uint8_t* __restrict__ y,
+                                                        int n, unsigned* __restrict__ rootcnt, u64* __restrict__ wtot,
+                                                        unsigned* __restrict__ rows) {
+  __shared__ unsigned c[kKP + 1];
+  const int j = blockIdx.y;
+  if (threadIdx.x <= kKP) c[threadIdx.x] = 0;
+  __syncthreads();
+  unsigned mine = 0;
+  for (int r = blockIdx.x * kTT + threadIdx.x; r < n; r += gridDim.x * kTT) {
+    const unsigned w = wts[(size_t)j * n + r];
+    if (w) {
+      atomicAdd(&c[y[r] & 7], w);
+      ++mine;
+    }
+  }
+  if (mine) atomicAdd(&c[kKP], mine);
+  __syncthreads();
+  if (threadIdx.x < kKP && c[threadIdx.x]) {
+    atomicAdd(&rootcnt[j * kKP + threadIdx.x], c[threadIdx.x]);
+    atomicAdd(&wtot[j], (u64)c[threadIdx.x]);
+  }
+  if (threadIdx.x == kKP && c[kKP]) atomicAdd(&rows[j], c[kKP]);
+}
+
 __device__ __forceinline__ void write_leaf_node(const Tables& o, int at, int cap_left, const unsigned* c, int n,
                                                 int depth) {
   if (cap_left <= 0) return;
@@ -257,7 +309,9 @@ __device__ __forceinline__ void write_leaf_node(const Tables& o, int at, int cap
 }
 
 // roots: node 0 of every job and the segments of level 0 (one per job)
-__global__ __launch_bounds__(kTT) void tt_init(Jobs jb, int J, int T, Segs sg, Tables o) {
+template <bool WT>
+__global__ __launch_bounds__(kTT) void tt_init(Jobs jb, int J, int T, Segs sg, Tables o, const u64* __restrict__ wtot,
+                                               const unsigned* __restrict__ rows) {
   const int j = blockIdx.x * kTT + threadIdx.x;
   if (j == 0) sg.begin[J] = T;
   if (j >= J) return;
@@ -269,9 +323,16 @@ __global__ __launch_bounds__(kTT) void tt_init(Jobs jb, int J, int T, Segs sg, T
   }
   for (int i = 0; i < j; ++i)
     for (int k = 0; k < kKP; ++k) base[k] += jb.rootcnt[i * kKP + k];
-  bool bad = n != (unsigned)jb.n[j];
+  bool bad;
+  int heavy = 0;
+  if constexpr (WT) {
+    bad = rows[j] != (unsigned)jb.n[j];
+    heavy = wtot[j] > (u64)VAD_TREE_TRAIN_MAX_WEIGHT || wtot[j] != (u64)n ? VAD_TREE_TRAIN_BAD_WEIGHT : 0;
+  } else {
+    bad = n != (unsigned)jb.n[j];
+  }
   for (int k = o.K; k < kKP; ++k) bad |= c[k] != 0;  // a label >= n_classes
-  o.status[j] = bad ? VAD_TREE_TRAIN_BAD_ROWS : 0;
+  o.status[j] = (bad ? VAD_TREE_TRAIN_BAD_ROWS : 0) | heavy;
   write_leaf_node(o, jb.nodeoff[j], jb.cap[j], c, jb.n[j], 0);
   o.n_nodes[j] = 1;
   sg.begin[j] = jb.off[j];
@@ -315,17 +376,63 @@ __global__ __launch_bounds__(kTT) void tt_class_tiles(const uint2* __restrict__ 
         (unsigned)(tot[threadIdx.x >> 2] >> (16 * (threadIdx.x & 3))) & 0xffffu;
 }
 
+// the weighted class counts of every (feature, tile): the weight of an entry
+// is gathered by (the job of its segment, its row)
+template <int WW>
+__global__ __launch_bounds__(kTT) void tt_class_tiles_w(const uint2* __restrict__ list, int Tp, int Tl,
+                                                        unsigned* __restrict__ tilecnt, int NT,
+                                                        const uint8_t* __restrict__ wts, int n,
+                                                        const int* __restrict__ sbegin, const int* __restrict__ sjob,
+                                                        int S) {
+  __shared__ u64 sh[kTT / 64];
+  __shared__ int rng[2];
+  const int t = blockIdx.x, f = blockIdx.y;
+  const int tile0 = t * kTile, q0 = tile0 + threadIdx.x * kTI;
+  tile_seg_range(sbegin, S, tile0, Tl, rng);
+  uint2 e[kTI];
+  load_items(list + (size_t)f * Tp, q0, Tl, e);
+  int s = q0 < Tl ? seg_of(sbegin, rng[0], rng[1], q0) : rng[1];
+  int send = sbegin[s + 1], job = sjob[s];
+  u64 pk[WW], tot[WW];
+#pragma unroll
+  for (int i = 0; i < WW; ++i) pk[i] = 0;
+#pragma unroll
+  for (int j = 0; j < kTI; ++j)
+    if (q0 + j < Tl) {
+      while (q0 + j >= send && s + 1 < S) {
+        ++s;
+        send = sbegin[s + 1];
+        job = sjob[s];
+      }
+      const unsigned r = e[j].y & kRowMask;
+      const unsigned w = r < (unsigned)n ? wts[(size_t)job * n + r] : 0u;
+      add_weight<WW>(pk, (e[j].y >> VAD_TREE_TRAIN_ROW_BITS) & 7, w);
+    }
+#pragma unroll
+  for (int i = 0; i < WW; ++i) block_excl_scan(pk[i], sh, tot[i]);
+  if (threadIdx.x < kKP) {
+    u64 word = 0;
+#pragma unroll
+    for (int i = 0; i < WW; ++i) word = (int)(threadIdx.x >> 1) == i ? tot[i] : word;
+    tilecnt[((size_t)f * NT + t) * kKP + threadIdx.x] = (unsigned)(word >> (32 * (threadIdx.x & 1)));
+  }
+}
+
 // NW: 64-bit words of packed 16-bit class counters (1: up to 4 classes).
 // MASKED: jfmask[job] has bit f set when the job may split on feature f
 // (vad_tree_train_features); a feature whose bit is clear in a segment's job
 // mask contributes no candidate to that segment, and a feature no segment of
 // the tile may use is not searched at all.  !MASKED is the kernel as it was.
-template <int NW, bool MASKED>
+// WW > 0: the weighted build (NW is then unused): WW words of 32-bit fields,
+// running counts add the gathered weights, the divisors are the weighted
+// totals of the two sides; positions and min_samples_leaf stay distinct rows.
+template <int NW, bool MASKED, int WW>
 __global__ __launch_bounds__(kTT) void tt_search(const uint2* __restrict__ list, int Tp, int Tl, int F, int fc,
                                                  const unsigned* __restrict__ tilecnt, int NT, Segs sg, int S,
                                                  const int* __restrict__ jmsl, const u64* __restrict__ jfmask,
-                                                 Rec* __restrict__ segbest, int Smax, Rec* __restrict__ tilefirst) {
-  constexpr int KK = 4 * NW;
+                                                 Rec* __restrict__ segbest, int Smax, Rec* __restrict__ tilefirst,
+                                                 const uint8_t* __restrict__ wts, int n) {
+  constexpr int KK = WW ? 2 * WW : 4 * NW;
   __shared__ u64 cur_score[kSegLds], best_score[kSegLds], best_key[kSegLds];
   __shared__ unsigned cur_p[kSegLds];
   __shared__ int seg_b[kSegLds + 1];
@@ -357,6 +464,12 @@ __global__ __launch_bounds__(kTT) void tt_search(const uint2* __restrict__ list,
       atomicOr(&fm_s[NS], m);
     }
   }
+  int* seg_j = nullptr;  // [NS] the segments' jobs (weighted: the row of the weight table)
+  if constexpr (WW > 0) {
+    __shared__ int sj_s[kSegLds];
+    seg_j = sj_s;
+    for (int i = tid; i < NS; i += kTT) sj_s[i] = sg.job[sLo + i];
+  }
   __syncthreads();
 
   // the segment of every item (the same in all features); items past the
@@ -387,14 +500,31 @@ __global__ __launch_bounds__(kTT) void tt_search(const uint2* __restrict__ list,
     const uint2* L = list + (size_t)f * Tp;
     uint2 e[kTI];
     load_items(L, q0, Tl, e);
-    u64 pk[2], ex[NW], tot;
-    pack_labels(e, q0, Tl, pk);
-#pragma unroll
-    for (int w = 0; w < NW; ++w) ex[w] = block_excl_scan(pk[w], sh, tot);
     unsigned run[KK];
     const unsigned* tc = tilecnt + ((size_t)f * NT + t) * kKP;
+    unsigned wv[WW ? kTI : 1];  // weighted: the items' weights
+    if constexpr (WW > 0) {
+      u64 pw[WW], ex[WW], tot;
 #pragma unroll
-    for (int k = 0; k < KK; ++k) run[k] = tc[k] + ((unsigned)(ex[k >> 2] >> (16 * (k & 3))) & 0xffffu);
+      for (int i = 0; i < WW; ++i) pw[i] = 0;
+#pragma unroll
+      for (int j = 0; j < kTI; ++j) {
+        const unsigned r = e[j].y & kRowMask;
+        wv[j] = q0 + j < Tl && in_table && r < (unsigned)n ? wts[(size_t)seg_j[sl[j]] * n + r] : 0u;
+        add_weight<WW>(pw, (e[j].y >> VAD_TREE_TRAIN_ROW_BITS) & 7, wv[j]);
+      }
+#pragma unroll
+      for (int i = 0; i < WW; ++i) ex[i] = block_excl_scan(pw[i], sh, tot);
+#pragma unroll
+      for (int k = 0; k < KK; ++k) run[k] = tc[k] + (unsigned)(ex[k >> 1] >> (32 * (k & 1)));
+    } else {
+      u64 pk[2], ex[NW], tot;
+      pack_labels(e, q0, Tl, pk);
+#pragma unroll
+      for (int w = 0; w < NW; ++w) ex[w] = block_excl_scan(pk[w], sh, tot);
+#pragma unroll
+      for (int k = 0; k < KK; ++k) run[k] = tc[k] + ((unsigned)(ex[k >> 2] >> (16 * (k & 3))) & 0xffffu);
+    }
     lastv[tid] = __uint_as_float(e[kTI - 1].x);
     __syncthreads();
     float pv = tid ? lastv[tid - 1] : (q0 > 0 && q0 < Tl ? __uint_as_float(L[q0 - 1].x) : 0.f);
@@ -421,19 +551,25 @@ __global__ __launch_bounds__(kTT) void tt_search(const uint2* __restrict__ list,
         const float v = __uint_as_float(e[j].x);
         const int p = q - c_begin;
         if (p >= 1 && v > pv && p >= c_msl && c_n - p >= c_msl) {
-          u64 sL = 0, sR = 0;
+          u64 sL = 0, sR = 0, wL = 0, wR = 0;
 #pragma unroll
           for (int k = 0; k < KK; ++k) {
             const u64 a = run[k] - c_base[k];
             const u64 b = c_cnt[k] - a;
             sL += a * a;
             sR += b * b;
+            wL += a;
+            wR += b;
           }
-          score = (double)sL / (double)p + (double)sR / (double)(c_n - p);
+          if constexpr (WW > 0) score = (double)sL / (double)wL + (double)sR / (double)wR;
+          else score = (double)sL / (double)p + (double)sR / (double)(c_n - p);
         }
         const unsigned lab = (e[j].y >> VAD_TREE_TRAIN_ROW_BITS) & 7;
 #pragma unroll
-        for (int k = 0; k < KK; ++k) run[k] += lab == (unsigned)k;
+        for (int k = 0; k < KK; ++k) {
+          if constexpr (WW > 0) run[k] += lab == (unsigned)k ? wv[j] : 0u;
+          else run[k] += lab == (unsigned)k;
+        }
         pv = v;
       }
       sc[j] = score;
@@ -518,25 +654,33 @@ __global__ __launch_bounds__(kTT) void tt_search(const uint2* __restrict__ list,
 }
 
 // ---- decide: one wave per segment --------------------------------------------
+// WT: the weighted build (purity by the total weight, children's class counts weighted)
+template <bool WT>
 __global__ __launch_bounds__(kTT) void tt_decide(const uint2* __restrict__ list, int Tp, Segs sg, int S, int level,
                                                  Jobs jb, const unsigned* __restrict__ tilecnt, int NT,
                                                  const Rec* __restrict__ segbest, int Smax,
                                                  const Rec* __restrict__ tilefirst, int ny, int* __restrict__ dec,
                                                  int* __restrict__ bf, int* __restrict__ bp,
-                                                 unsigned* __restrict__ cl, Tables o) {
+                                                 unsigned* __restrict__ cl, Tables o,
+                                                 const uint8_t* __restrict__ wts, int nrows) {
   const int lane = threadIdx.x & 63;
   const int s = blockIdx.x * (kTT / 64) + (threadIdx.x >> 6);
   if (s >= S) return;
   const int begin = sg.begin[s], n = sg.begin[s + 1] - begin, job = sg.job[s];
   const int md = jb.md[job], mss = jb.mss[job], msl = jb.msl[job];
-  unsigned cnt[kKP], maxc = 0;
+  unsigned cnt[kKP], maxc = 0, W = 0;
 #pragma unroll
   for (int k = 0; k < kKP; ++k) {
     cnt[k] = sg.cnt[(size_t)s * kKP + k];
     maxc = max(maxc, cnt[k]);
+    W += cnt[k];
   }
   if (lane == 0) dec[s] = 0;
-  if (!child_live(level, n, maxc, md, mss, msl)) return;
+  if constexpr (WT) {
+    if (!child_live_w(level, n, maxc, W, md, mss, msl)) return;
+  } else {
+    if (!child_live(level, n, maxc, md, mss, msl)) return;
+  }
 
   // exact lexicographic maximum of the records: score, then lowest (f, p)
   const int t0 = begin / kTile, nt = (begin + n - 1) / kTile - t0 + 1;
@@ -566,24 +710,35 @@ __global__ __launch_bounds__(kTT) void tt_decide(const uint2* __restrict__ list,
 
   // left class counts: the running counts at q less the segment's base
   const int tq = q / kTile, lo = max(tq * kTile, begin);
-  u64 pk[2] = {0, 0};
+  u64 pk[2] = {0, 0}, pw[4] = {0, 0, 0, 0};
   for (int i = lo + lane; i < q; i += 64) {
-    const unsigned lab = (L[i].y >> VAD_TREE_TRAIN_ROW_BITS) & 7;
-    pk[lab >> 2] += 1ull << (16 * (lab & 3));
+    const unsigned ey = L[i].y, lab = (ey >> VAD_TREE_TRAIN_ROW_BITS) & 7;
+    if constexpr (WT) {
+      const unsigned r = ey & kRowMask;
+      add_weight<4>(pw, lab, r < (unsigned)nrows ? wts[(size_t)job * nrows + r] : 0u);
+    } else {
+      pk[lab >> 2] += 1ull << (16 * (lab & 3));
+    }
   }
 #pragma unroll
   for (int d = 32; d; d >>= 1) {
-    pk[0] += __shfl_xor(pk[0], d);
-    pk[1] += __shfl_xor(pk[1], d);
+    if constexpr (WT) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) pw[i] += __shfl_xor(pw[i], d);
+    } else {
+      pk[0] += __shfl_xor(pk[0], d);
+      pk[1] += __shfl_xor(pk[1], d);
+    }
   }
-  unsigned cL[kKP], maxL = 0, maxR = 0;
+  unsigned cL[kKP], maxL = 0, maxR = 0, WL = 0;
 #pragma unroll
   for (int k = 0; k < kKP; ++k) {
-    unsigned v = (unsigned)(pk[k >> 2] >> (16 * (k & 3))) & 0xffffu;
+    unsigned v = WT ? (unsigned)(pw[k >> 1] >> (32 * (k & 1))) : (unsigned)(pk[k >> 2] >> (16 * (k & 3))) & 0xffffu;
     if (begin < tq * kTile) v += tilecnt[((size_t)f * NT + tq) * kKP + k] - sg.base[(size_t)s * kKP + k];
     cL[k] = min(v, cnt[k]);
     maxL = max(maxL, cL[k]);
     maxR = max(maxR, cnt[k] - cL[k]);
+    WL += cL[k];
   }
   if (lane != 0) return;
   const double x0 = (double)__uint_as_float(L[q - 1].x), x1 = (double)__uint_as_float(L[q].x);
@@ -596,8 +751,12 @@ __global__ __launch_bounds__(kTT) void tt_decide(const uint2* __restrict__ list,
     o.threshold[at] = thr;
     o.nan_left[at] = nL > nR;
   }
-  dec[s] = 1 | (child_live(level + 1, nL, maxL, md, mss, msl) ? 2 : 0) |
-           (child_live(level + 1, nR, maxR, md, mss, msl) ? 4 : 0);
+  if constexpr (WT)
+    dec[s] = 1 | (child_live_w(level + 1, nL, maxL, WL, md, mss, msl) ? 2 : 0) |
+             (child_live_w(level + 1, nR, maxR, W - WL, md, mss, msl) ? 4 : 0);
+  else
+    dec[s] = 1 | (child_live(level + 1, nL, maxL, md, mss, msl) ? 2 : 0) |
+             (child_live(level + 1, nR, maxR, md, mss, msl) ? 4 : 0);
   bf[s] = f;
   bp[s] = p;
 #pragma unroll
@@ -837,7 +996,7 @@ struct Layout {
   int64_t T = 0, Tp = 0;
   int NT = 0, NTn = 0, Smax = 0, ny = 1, fc = 1;
   size_t list[2], flags, tilecnt, ptile, ftile, segbest, tilefirst, seg[2][5], dec, bf, bp, cl, E, jobi, rootcnt,
-      summary, fmask, total;
+      summary, fmask, wtot, wrows, total;
 };
 
 inline size_t carve(size_t& at, size_t bytes) {
@@ -846,7 +1005,7 @@ inline size_t carve(size_t& at, size_t bytes) {
   return o;
 }
 
-bool make_layout(int64_t n, int F, int J, const vad_tree_job* jobs, Layout& L) {
+bool make_layout(int64_t n, int F, int J, const vad_tree_job* jobs, bool weighted, Layout& L) {
   int64_t T = 0, smax = 0;
   for (int j = 0; j < J; ++j) {
     T += jobs[j].n_rows;
@@ -892,15 +1051,20 @@ bool make_layout(int64_t n, int F, int J, const vad_tree_job* jobs, Layout& L) {
   L.rootcnt = carve(at, (size_t)J * kKP * 4);
   L.summary = carve(at, 256);
   L.fmask = carve(at, (size_t)J * 8);
+  L.wtot = L.wrows = at;
+  if (weighted) {  // the roots' total weights and distinct rows
+    L.wtot = carve(at, (size_t)J * 8);
+    L.wrows = carve(at, (size_t)J * 4);
+  }
   L.total = at;
   return true;
 }
 
 }  // namespace
 
-size_t tree_train_ws_bytes(int64_t n, int F, int n_jobs, const vad_tree_job* jobs) {
+size_t tree_train_ws_bytes(int64_t n, int F, int n_jobs, const vad_tree_job* jobs, bool weighted) {
   Layout L;
-  return make_layout(n, F, n_jobs, jobs, L) ? L.total : 0;
+  return make_layout(n, F, n_jobs, jobs, weighted, L) ? L.total : 0;
 }
 
 #define TT_CHECK(e)                         \
@@ -911,9 +1075,11 @@ size_t tree_train_ws_bytes(int64_t n, int F, int n_jobs, const vad_tree_job* job
 
 int tree_train_run(const float* x, const uint8_t* y, int64_t n64, int F, int K, const int32_t* order,
                    const uint8_t* mask, const uint64_t* feature_masks, int J, const vad_tree_job* jobs,
-                   const vad_tree_tables& out, void* ws, size_t ws_bytes, int32_t* n_levels, hipStream_t st) {
+                   const vad_tree_tables& out, void* ws, size_t ws_bytes, int32_t* n_levels, hipStream_t st,
+                   bool weighted) {
+  // weighted: mask holds the jobs' weights (not NULL)
   Layout L;
-  if (!make_layout(n64, F, J, jobs, L) || ws_bytes < L.total) return VAD_EINVAL;
+  if (!make_layout(n64, F, J, jobs, weighted, L) || ws_bytes < L.total || (weighted && !mask)) return VAD_EINVAL;
   const int n = (int)n64, T = (int)L.T, Tp = (int)L.Tp;
   char* w = (char*)ws;
 
@@ -998,30 +1164,54 @@ int tree_train_run(const float* x, const uint8_t* y, int64_t n64, int F, int K, 
   hipLaunchKernelGGL(tt_carry<1>, dim3(J * F), dim3(kTT), 0, st, ftile, L.NTn, L.NTn);
   hipLaunchKernelGGL(tt_filter<true>, fgrid, dim3(kTT), 0, st, order, mask, x, y, n, F, L.NTn, ftile, jb.off, jb.n,
                      list[0], Tp);
-  hipLaunchKernelGGL(tt_root_counts, dim3(L.NTn < 1024 ? L.NTn : 1024, J), dim3(kTT), 0, st, mask, y, n, jb.rootcnt);
-  hipLaunchKernelGGL(tt_init, dim3((J + kTT - 1) / kTT), dim3(kTT), 0, st, jb, J, T, sg[0], o);
+  if (weighted) {
+    u64* wtot = (u64*)(w + L.wtot);
+    unsigned* wrows = (unsigned*)(w + L.wrows);
+    TT_CHECK(hipMemsetAsync(wtot, 0, L.total - L.wtot, st));
+    hipLaunchKernelGGL(tt_root_counts_w, dim3(L.NTn < 1024 ? L.NTn : 1024, J), dim3(kTT), 0, st, mask, y, n,
+                       jb.rootcnt, wtot, wrows);
+    hipLaunchKernelGGL(tt_init<true>, dim3((J + kTT - 1) / kTT), dim3(kTT), 0, st, jb, J, T, sg[0], o, wtot, wrows);
+  } else {
+    hipLaunchKernelGGL(tt_root_counts, dim3(L.NTn < 1024 ? L.NTn : 1024, J), dim3(kTT), 0, st, mask, y, n, jb.rootcnt);
+    hipLaunchKernelGGL(tt_init<false>, dim3((J + kTT - 1) / kTT), dim3(kTT), 0, st, jb, J, T, sg[0], o,
+                       (const u64*)nullptr, (const unsigned*)nullptr);
+  }
   TT_CHECK(hipGetLastError());
 
   int S = J, Tl = T, par = 0, cur = 0, level = 0;
   for (; S > 0 && level <= max_depth; ++level) {
     const int NTl = (Tl + kTile - 1) / kTile;
-    hipLaunchKernelGGL(tt_class_tiles, dim3(NTl, F), dim3(kTT), 0, st, list[cur], Tp, Tl, tilecnt, L.NT);
-    hipLaunchKernelGGL(tt_carry<kKP>, dim3(F), dim3(kTT), 0, st, tilecnt, NTl, L.NT);
     const dim3 sgrid(NTl, L.ny);
-    if (K <= 4 && !jfmask)
-      hipLaunchKernelGGL((tt_search<1, false>), sgrid, dim3(kTT), 0, st, list[cur], Tp, Tl, F, L.fc, tilecnt, L.NT,
-                         sg[par], S, jb.msl, jfmask, segbest, L.Smax, tilefirst);
-    else if (!jfmask)
-      hipLaunchKernelGGL((tt_search<2, false>), sgrid, dim3(kTT), 0, st, list[cur], Tp, Tl, F, L.fc, tilecnt, L.NT,
-                         sg[par], S, jb.msl, jfmask, segbest, L.Smax, tilefirst);
-    else if (K <= 4)
-      hipLaunchKernelGGL((tt_search<1, true>), sgrid, dim3(kTT), 0, st, list[cur], Tp, Tl, F, L.fc, tilecnt, L.NT,
-                         sg[par], S, jb.msl, jfmask, segbest, L.Smax, tilefirst);
-    else
-      hipLaunchKernelGGL((tt_search<2, true>), sgrid, dim3(kTT), 0, st, list[cur], Tp, Tl, F, L.fc, tilecnt, L.NT,
-                         sg[par], S, jb.msl, jfmask, segbest, L.Smax, tilefirst);
-    hipLaunchKernelGGL(tt_decide, dim3((S + 3) / 4), dim3(kTT), 0, st, list[cur], Tp, sg[par], S, level, jb, tilecnt,
-                       L.NT, segbest, L.Smax, tilefirst, L.ny, dec, bf, bp, cl, o);
+#define TT_SEARCH(NW, MASKED, WW)                                                                                  \
+  hipLaunchKernelGGL((tt_search<NW, MASKED, WW>), sgrid, dim3(kTT), 0, st, list[cur], Tp, Tl, F, L.fc, tilecnt, L.NT, \
+                     sg[par], S, jb.msl, jfmask, segbest, L.Smax, tilefirst, mask, n)
+#define TT_CLASS_W(WW)                                                                                        \
+  hipLaunchKernelGGL(tt_class_tiles_w<WW>, dim3(NTl, F), dim3(kTT), 0, st, list[cur], Tp, Tl, tilecnt, L.NT, mask, n, \
+                     sg[par].begin, sg[par].job, S)
+    if (!weighted) hipLaunchKernelGGL(tt_class_tiles, dim3(NTl, F), dim3(kTT), 0, st, list[cur], Tp, Tl, tilecnt, L.NT);
+    else if (K <= 2) TT_CLASS_W(1);
+    else if (K <= 4) TT_CLASS_W(2);
+    else TT_CLASS_W(4);
+    hipLaunchKernelGGL(tt_carry<kKP>, dim3(F), dim3(kTT), 0, st, tilecnt, NTl, L.NT);
+    if (!weighted) {
+      if (K <= 4 && !jfmask) TT_SEARCH(1, false, 0);
+      else if (!jfmask) TT_SEARCH(2, false, 0);
+      else if (K <= 4) TT_SEARCH(1, true, 0);
+      else TT_SEARCH(2, true, 0);
+      hipLaunchKernelGGL(tt_decide<false>, dim3((S + 3) / 4), dim3(kTT), 0, st, list[cur], Tp, sg[par], S, level, jb,
+                         tilecnt, L.NT, segbest, L.Smax, tilefirst, L.ny, dec, bf, bp, cl, o, mask, n);
+    } else {
+      if (K <= 2 && !jfmask) TT_SEARCH(1, false, 1);
+      else if (K <= 4 && !jfmask) TT_SEARCH(1, false, 2);
+      else if (!jfmask) TT_SEARCH(1, false, 4);
+      else if (K <= 2) TT_SEARCH(1, true, 1);
+      else if (K <= 4) TT_SEARCH(1, true, 2);
+      else TT_SEARCH(1, true, 4);
+      hipLaunchKernelGGL(tt_decide<true>, dim3((S + 3) / 4), dim3(kTT), 0, st, list[cur], Tp, sg[par], S, level, jb,
+                         tilecnt, L.NT, segbest, L.Smax, tilefirst, L.ny, dec, bf, bp, cl, o, mask, n);
+    }
+#undef TT_SEARCH
+#undef TT_CLASS_W
     hipLaunchKernelGGL(tt_scan, dim3(1), dim3(kTT), 0, st, sg[par], S, jb, J, par, dec, bp, cl, E, Estride, summary,
                        o.status);
     hipLaunchKernelGGL(tt_emit, dim3((S + J + kTT - 1) / kTT), dim3(kTT), 0, st, sg[par], S, level, jb, J, par, dec,
@@ -1052,7 +1242,7 @@ int tree_train_run(const float* x, const uint8_t* y, int64_t n64, int F, int K, 
   TT_CHECK(hipStreamSynchronize(st));
   int rc = VAD_OK;
   for (int j = 0; j < J; ++j) {
-    if (status[j] & VAD_TREE_TRAIN_BAD_ROWS) return VAD_EINVAL;
+    if (status[j] & (VAD_TREE_TRAIN_BAD_ROWS | VAD_TREE_TRAIN_BAD_WEIGHT)) return VAD_EINVAL;
     if (status[j] & VAD_TREE_TRAIN_OVERFLOW) rc = VAD_ENOMEM;
   }
   return rc;

@@ -387,12 +387,15 @@ hipError_t launch_ffn_eval(int n_layers, const int32_t* dims, const float* state
 
 // Decision-tree training (tree_train_kernel.hip).  The C entries have checked
 // every argument; tree_train_ws_bytes is 0 where the sizes do not fit.
-size_t tree_train_ws_bytes(int64_t n, int F, int n_jobs, const vad_tree_job* jobs);
+// weighted: the sizes of the weighted build (a little more than the unweighted).
+size_t tree_train_ws_bytes(int64_t n, int F, int n_jobs, const vad_tree_job* jobs, bool weighted = false);
 // feature_masks (host, one word per job; null: every feature): bit f set when
-// the job may split on feature f.
+// the job may split on feature f.  weighted: mask holds one uint8 weight per
+// (job, row), not null, and the weighted kernels run.
 int tree_train_run(const float* x, const uint8_t* y, int64_t n, int F, int K, const int32_t* order,
                    const uint8_t* mask, const uint64_t* feature_masks, int n_jobs, const vad_tree_job* jobs,
-                   const vad_tree_tables& out, void* ws, size_t ws_bytes, int32_t* n_levels, hipStream_t st);
+                   const vad_tree_tables& out, void* ws, size_t ws_bytes, int32_t* n_levels, hipStream_t st,
+                   bool weighted = false);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel and device
 // (`done`: one bit per device ordinal, a static of the launch site).

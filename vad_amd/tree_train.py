@@ -26,6 +26,17 @@ sampled without replacement and a feature subset per tree, drawn on the host
 (``forest_draws``), all trees in one call; it returns a
 ``vad_amd.forest.ForestClassifier``.
 
+Rows may carry integer weights (a sixth element of a job; ``sample_weight=``
+and ``class_weight=`` of ``fit``, ``fit_forest`` and ``grid``): the tree is
+sklearn's ``fit(X, y, sample_weight=w)``.  Distinct rows go on counting for
+``n_node_samples`` and the three parameters; class counts, scores, purity and
+``value`` are weighted.  A row weighs at most 255 and a
+job at most 2^26 in all, so that every sum is an exact integer.
+``fit_forest(bootstrap=True)`` draws rows WITH replacement, as sklearn's
+``RandomForestClassifier`` does: tree t is fitted with the counts of its draw
+as weights.  ``balanced_integer_weights`` gives integer class weights in the
+proportions of ``class_weight="balanced"``.
+
 There is no CPU path: the trees grow in the HIP kernels or the call raises.
 """
 from __future__ import annotations
@@ -42,6 +53,8 @@ from .tree import TreeClassifier
 MAX_FEATURES = 64
 MAX_CLASSES = 8
 MAX_ROWS = 1 << 27
+MAX_ROW_WEIGHT = 255
+MAX_TOTAL_WEIGHT = 1 << 26
 
 
 class _Job(ctypes.Structure):
@@ -107,6 +120,90 @@ def check_rows(X, y):
     if len(classes) > MAX_CLASSES:
         raise ValueError(f"{len(classes)} classes, at most {MAX_CLASSES}")
     return Xc, idx.astype(np.uint8).reshape(n), classes
+
+
+def check_job_weights(w, n):
+    """A job's row weights: an integer array (n,) of 0..255 with at least one
+    above 0 and at most 2^26 in all (ValueError); returns it as uint8."""
+    w = np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w)
+    if w.dtype.kind not in "iu":
+        raise ValueError(f"row weights must be integers, got dtype {w.dtype} (float weights are not supported)")
+    if w.shape != (int(n),):
+        raise ValueError(f"row weights must be ({int(n)},), got {w.shape}")
+    if w.size and w.min() < 0:
+        raise ValueError("row weights must be >= 0")
+    if not (w > 0).any():
+        raise ValueError("row weights need at least one row above 0")
+    if w.max() > MAX_ROW_WEIGHT:
+        raise ValueError(f"a row's weight (sample_weight * class_weight) must be <= {MAX_ROW_WEIGHT}, got {int(w.max())}")
+    total = int(w.astype(np.int64).sum())
+    if total > MAX_TOTAL_WEIGHT:
+        raise ValueError(f"the total weight of a tree's rows must be <= 2^26, got {total}")
+    return w.astype(np.uint8)
+
+
+def row_weights(y, classes, sample_weight=None, class_weight=None):
+    """``sample_weight[i] * class_weight[y[i]]`` as int64 (n,), or None when
+    both are None.  ``sample_weight``: integers (n,), >= 0; ``class_weight``:
+    {class value: positive int} with exactly the keys ``classes``.  Every
+    violation is a ValueError; the limits of the product are
+    ``check_job_weights``'s."""
+    if sample_weight is None and class_weight is None:
+        return None
+    y = np.asarray(y)
+    n = len(y)
+    w = np.ones(n, np.int64)
+    if sample_weight is not None:
+        sw = np.asarray(sample_weight.cpu() if isinstance(sample_weight, torch.Tensor) else sample_weight)
+        if sw.dtype.kind not in "iu":
+            raise ValueError(f"sample_weight must be integers, got dtype {sw.dtype} (float weights are not supported)")
+        if sw.shape != (n,):
+            raise ValueError(f"sample_weight must be ({n},), got {sw.shape}")
+        if n and sw.min() < 0:
+            raise ValueError("sample_weight must be >= 0")
+        if not (sw > 0).any():
+            raise ValueError("sample_weight needs at least one row above 0")
+        if sw.max() > MAX_TOTAL_WEIGHT:
+            raise ValueError("sample_weight is past the limits: a row's weight must be <= 255")
+        w = sw.astype(np.int64)
+    if class_weight is not None:
+        if isinstance(class_weight, str):
+            raise ValueError(f"class_weight={class_weight!r} is not supported: the weights must be integers; "
+                             "balanced_integer_weights(y) gives a dict in the proportions of \"balanced\"")
+        if not isinstance(class_weight, dict):
+            raise ValueError("class_weight must be a dict {class value: positive int}")
+        keys = list(class_weight)
+        want = np.asarray(classes).tolist()
+        if len(keys) != len(want) or any(k not in keys for k in want):
+            raise ValueError(f"class_weight must have exactly the classes {want} as keys, got {keys}")
+        cw = np.zeros(len(want), np.int64)
+        for i, k in enumerate(want):
+            v = class_weight[k]
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+                raise ValueError(f"class_weight[{k!r}] must be a positive integer, got {v!r}")
+            if int(v) > MAX_ROW_WEIGHT:
+                raise ValueError(f"class_weight[{k!r}] must be <= {MAX_ROW_WEIGHT}, got {v!r}")
+            cw[i] = int(v)
+        w = w * cw[np.searchsorted(np.asarray(classes), y)]
+    return w
+
+
+def balanced_integer_weights(y, max_weight=255):
+    """Integer class weights in the proportions of sklearn's
+    ``class_weight="balanced"`` (n / (K * count_k)): {class:
+    clip(round(max_count / count_k), 1, max_weight)}, the most frequent class
+    at 1 (``round`` to the nearest, halves to even).  Scaling all weights by a
+    constant does not change a Gini tree, so only the proportions matter; they
+    are met to the rounding."""
+    max_weight = int(max_weight)
+    if not 1 <= max_weight <= MAX_ROW_WEIGHT:
+        raise ValueError(f"max_weight must be 1..{MAX_ROW_WEIGHT}")
+    yh = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
+    if yh.ndim != 1 or yh.size < 1:
+        raise ValueError("y must be a non-empty 1-D array")
+    classes, counts = np.unique(yh, return_counts=True)
+    top = int(counts.max())
+    return {c.item(): int(min(max(round(top / int(k)), 1), max_weight)) for c, k in zip(classes, counts)}
 
 
 def preorder(t):
@@ -192,7 +289,7 @@ def feature_mask(features, F):
     return int(sum(1 << int(i) for i in f))
 
 
-def forest_draws(n, F, n_trees, max_samples=1.0, max_features="sqrt", seed=0):
+def forest_draws(n, F, n_trees, max_samples=1.0, max_features="sqrt", seed=0, bootstrap=False):
     """The row and feature subsets ``fit_forest`` trains tree t on, as
     [(rows_t, feats_t), ...] (None: all).  ``rng = np.random.default_rng(seed)``;
     for t = 0 .. n_trees-1 in order
@@ -201,7 +298,12 @@ def forest_draws(n, F, n_trees, max_samples=1.0, max_features="sqrt", seed=0):
     ``feats_t = np.sort(rng.choice(F, k, replace=False))`` with k =
     max(1, int(sqrt(F))) for "sqrt", max(1, int(max_features * F)) for a
     float, the integer itself, F for None.  Both draws are always made; a draw
-    of everything (m == n, k == F) is then reported as None."""
+    of everything (m == n, k == F) is then reported as None.
+
+    ``bootstrap=True`` draws the rows WITH replacement instead: in the same
+    per-tree order, ``rows_t = np.bincount(rng.integers(0, n, m), minlength=n)``
+    -- the (n,) counts of the draw, the tree's row weights, never None -- then
+    the feature draw as above."""
     n, F, n_trees = int(n), int(F), int(n_trees)
     if n_trees < 1:
         raise ValueError("n_trees must be >= 1")
@@ -228,9 +330,12 @@ def forest_draws(n, F, n_trees, max_samples=1.0, max_features="sqrt", seed=0):
     rng = np.random.default_rng(seed)
     draws = []
     for _ in range(n_trees):
-        rows = np.sort(rng.choice(n, m, replace=False))
+        if bootstrap:
+            rows = np.bincount(rng.integers(0, n, m), minlength=n)
+        else:
+            rows = np.sort(rng.choice(n, m, replace=False))
         feats = np.sort(rng.choice(F, k, replace=False))
-        draws.append((None if m == n else rows, None if k == F else feats))
+        draws.append((rows if bootstrap or m != n else None, None if k == F else feats))
     return draws
 
 
@@ -243,8 +348,18 @@ class TreeTrainer:
         self.last_levels = None  # levels the last call ran (its deepest tree + 1)
         self.last_call_seconds = None  # host clock around the last vad_tree_train (it returns when the stream has run it)
 
-    def fit(self, X, y):
-        return self.fit_many(X, y, [(None, self.max_depth, self.min_samples_split, self.min_samples_leaf)])[0]
+    def fit(self, X, y, sample_weight=None, class_weight=None):
+        """The tree of the rows; with ``sample_weight`` (integers (n,), >= 0)
+        and / or ``class_weight`` ({class value: positive int}) the tree of
+        sklearn's ``fit(X, y, sample_weight=sample_weight * class_weight[y])``."""
+        job = (None, self.max_depth, self.min_samples_split, self.min_samples_leaf)
+        if sample_weight is None and class_weight is None:
+            return self.fit_many(X, y, [job])[0]
+        Xc, yi, classes = check_rows(X, y)
+        w = check_job_weights(row_weights(classes[yi], classes, sample_weight, class_weight), len(yi))
+        tree = self.fit_many(Xc, yi, [job + (None, w)])[0]
+        tree.classes_ = classes  # fit_many saw class indices
+        return tree
 
     def fit_many(self, X, y, jobs, node_capacity=None):
         """One tree per job ``(rows, max_depth, min_samples_split,
@@ -253,6 +368,11 @@ class TreeTrainer:
         repeats, in any order, or None for all; ``features``: the distinct
         columns the job may split on, or None for all (the tree is the one of
         ``X[:, features]`` with its feature indices mapped back).
+        A sixth element ``weights`` (after ``features``, which may be None)
+        gives the job integer row weights (n,), 0 for a row that is not in the
+        job; ``rows`` must then be None.  Jobs with and without weights mix: a
+        job without gets ones on its rows.  A call in which no job has weights
+        is the unweighted call.
         ``node_capacity`` (tests): nodes to provide per job instead of the
         bound that always suffices."""
         Xc, yi, classes = check_rows(X, y)
@@ -260,13 +380,19 @@ class TreeTrainer:
         K = max(2, len(classes))
         if not jobs:
             return []
-        params, row_sets, fmasks = [], [], []
+        params, row_sets, fmasks, weights = [], [], [], []
         for job in jobs:
-            if len(job) not in (4, 5):
-                raise ValueError("a job is (rows, max_depth, min_samples_split, min_samples_leaf[, features])")
+            if len(job) not in (4, 5, 6):
+                raise ValueError("a job is (rows, max_depth, min_samples_split, min_samples_leaf[, features[, weights]])")
             rows, md, mss, msl = job[:4]
-            fmasks.append(feature_mask(job[4] if len(job) == 5 else None, F))
+            fmasks.append(feature_mask(job[4] if len(job) >= 5 else None, F))
             params.append(check_params(md, mss, msl))
+            wj = job[5] if len(job) == 6 else None
+            if wj is not None:
+                if rows is not None:
+                    raise ValueError("a job with weights takes rows=None: a weight of 0 leaves a row out")
+                wj = check_job_weights(wj, n)
+            weights.append(wj)
             if rows is not None:
                 rows = np.asarray(rows.cpu() if isinstance(rows, torch.Tensor) else rows).astype(np.int64).ravel()
                 if rows.size < 1 or rows.min() < 0 or rows.max() >= n or np.unique(rows).size != rows.size:
@@ -280,21 +406,27 @@ class TreeTrainer:
             yd = torch.from_numpy(yi).to(dev)
             order = torch.sort(Xd.t().contiguous(), dim=1, stable=True).indices.to(torch.int32).contiguous()
             J = len(jobs)
+            weighted = any(wj is not None for wj in weights)
             mask = None
-            if any(r is not None for r in row_sets):
+            if weighted or any(r is not None for r in row_sets):
                 mask = torch.zeros((J, n), dtype=torch.uint8, device=dev)
                 for j, r in enumerate(row_sets):
-                    if r is None:
+                    if weights[j] is not None:
+                        mask[j] = torch.from_numpy(weights[j]).to(dev)
+                    elif r is None:
                         mask[j] = 1
                     else:
                         mask[j, torch.from_numpy(r).to(dev)] = 1
             desc = (_Job * J)()
             for j, ((md, mss, msl), r) in enumerate(zip(params, row_sets)):
                 nr = n if r is None else int(r.size)
+                if weights[j] is not None:
+                    nr = int(np.count_nonzero(weights[j]))
                 cap = int(lib().vad_tree_train_node_capacity(nr, msl)) if node_capacity is None else int(node_capacity)
                 desc[j] = _Job(nr, cap, md, mss, msl, 0)
             total = sum(int(d.node_capacity) for d in desc)
-            need = int(lib().vad_tree_train_workspace_bytes(n, F, K, J, desc))
+            ws_bytes = lib().vad_tree_train_weighted_workspace_bytes if weighted else lib().vad_tree_train_workspace_bytes
+            need = int(ws_bytes(n, F, K, J, desc))
             if need == 0:
                 raise ValueError("vad_tree_train refuses these sizes (include/vad_amd.h lists the limits)")
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -307,10 +439,10 @@ class TreeTrainer:
             fm = None
             if any(m is not None for m in fmasks):
                 fm = (ctypes.c_uint64 * J)(*((1 << F) - 1 if m is None else m for m in fmasks))
-            rc = lib().vad_tree_train_features(Xd.data_ptr(), yd.data_ptr(), n, F, K, order.data_ptr(),
-                                               None if mask is None else mask.data_ptr(), fm, J, desc,
-                                               ctypes.byref(tb), ws.data_ptr(), need, ctypes.byref(levels),
-                                               stream_ptr())
+            train = lib().vad_tree_train_weighted if weighted else lib().vad_tree_train_features
+            rc = train(Xd.data_ptr(), yd.data_ptr(), n, F, K, order.data_ptr(),
+                       None if mask is None else mask.data_ptr(), fm, J, desc, ctypes.byref(tb), ws.data_ptr(), need,
+                       ctypes.byref(levels), stream_ptr())
             self.last_call_seconds = time.perf_counter() - t0
             if rc == VAD_ENOMEM:
                 status = out["status"].cpu().numpy()
@@ -328,21 +460,38 @@ class TreeTrainer:
                                         depth=t["depth"], value=t["value"][:, :max(len(classes), 1)]))
         return trees
 
-    def fit_forest(self, X, y, n_trees, max_samples=1.0, max_features="sqrt", seed=0):
+    def fit_forest(self, X, y, n_trees, max_samples=1.0, max_features="sqrt", seed=0, bootstrap=False,
+                   class_weight=None):
         """A ForestClassifier of ``n_trees`` trees with the trainer's three
         parameters, tree t on the rows and features of ``forest_draws`` (drawn
-        on the host, WITHOUT replacement), all in one ``fit_many`` call."""
+        on the host; WITHOUT replacement, or with ``bootstrap=True`` WITH, the
+        counts of the draw as the tree's row weights), all in one ``fit_many``
+        call.  ``class_weight`` ({class value: positive int}) is multiplied
+        into every tree's weights."""
         from .forest import ForestClassifier
         Xc, yi, classes = check_rows(X, y)
         n, F = (int(v) for v in Xc.shape)
-        draws = forest_draws(n, F, n_trees, max_samples, max_features, seed)
-        jobs = [(r, self.max_depth, self.min_samples_split, self.min_samples_leaf, f) for r, f in draws]
+        cw = row_weights(classes[yi], classes, None, class_weight)
+        draws = forest_draws(n, F, n_trees, max_samples, max_features, seed, bootstrap)
+        p = (self.max_depth, self.min_samples_split, self.min_samples_leaf)
+        jobs = []
+        for r, f in draws:
+            if not bootstrap and cw is None:
+                jobs.append((r,) + p + (f,))
+                continue
+            if bootstrap:
+                w = r.astype(np.int64)
+            else:
+                w = np.zeros(n, np.int64)
+                w[slice(None) if r is None else r] = 1
+            jobs.append((None,) + p + (f, check_job_weights(w if cw is None else w * cw, n)))
         trees = self.fit_many(Xc, yi, jobs)
         for t in trees:  # fit_many saw class indices
             t.classes_ = classes
         return ForestClassifier.from_trees(trees)
 
-    def grid(self, X, y, max_depth, min_samples_split, min_samples_leaf, folds):
+    def grid(self, X, y, max_depth, min_samples_split, min_samples_leaf, folds, sample_weight=None,
+             class_weight=None):
         """Cross-validated accuracy of every (max_depth, min_samples_split,
         min_samples_leaf) over the caller's ``folds`` [(train_idx, test_idx),
         ...] (``kfold`` gives sklearn's).  One device job per (fold,
@@ -350,7 +499,10 @@ class TreeTrainer:
         min_samples_split; the other settings are pruned from it.  Returns a
         dict: "params" (list of dicts, in sklearn's ParameterGrid order),
         "mean_test_score", "best_index_", "best_params_", "best_score_" (the
-        first maximum, as GridSearchCV ranks)."""
+        first maximum, as GridSearchCV ranks).  ``sample_weight`` /
+        ``class_weight`` (as in ``fit``) weigh the training rows of every fold;
+        the score stays plain accuracy.  Pruning still holds: ``max_depth``
+        and ``min_samples_split`` act on distinct rows."""
         mds = [int(v) for v in np.atleast_1d(max_depth)]
         msss = [int(v) for v in np.atleast_1d(min_samples_split)]
         msls = [int(v) for v in np.atleast_1d(min_samples_leaf)]
@@ -358,7 +510,18 @@ class TreeTrainer:
         if not (mds and msss and msls and folds):
             raise ValueError("grid needs at least one value per parameter and one fold")
         Xc, yi, classes = check_rows(X, y)
-        jobs = [(tr, max(mds), min(msss), msl) for tr, _ in folds for msl in msls]
+        w = row_weights(classes[yi], classes, sample_weight, class_weight)
+        if w is None:
+            jobs = [(tr, max(mds), min(msss), msl) for tr, _ in folds for msl in msls]
+        else:
+            jobs = []
+            for tr, _ in folds:
+                if tr.size < 1 or tr.min() < 0 or tr.max() >= len(yi) or np.unique(tr).size != tr.size:
+                    raise ValueError("a fold's training rows must be distinct indices into X, at least one")
+                wf = np.zeros(len(yi), np.int64)
+                wf[tr] = w[tr]
+                wf = check_job_weights(wf, len(yi))
+                jobs += [(None, max(mds), min(msss), msl, None, wf) for msl in msls]
         big = self.fit_many(Xc, yi, jobs)
         dev = torch.device("cuda", torch.cuda.current_device())
         Xd = Xc if isinstance(Xc, torch.Tensor) and Xc.is_cuda else torch.as_tensor(Xc).to(dev)
